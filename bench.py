@@ -8,7 +8,7 @@ Sun Temple stand-in (~0.6 M triangles, seed 2), 1920x1080 visible + 64-px guard 
 (2048x1208 frame buffer), 1/4-res SD map (768x558 texels incl. the 128-texel SD guard),
 N = 4, MAX_COUNT = 8.  Inputs (BVH, G-buffer) are resident in HBM before timing.
 
-Two timed regions, each K frames between a barrier + torch.cuda.synchronize() pair:
+Two timed regions, each between a barrier + torch.cuda.synchronize() pair:
 
   latency    one frame in flight (the reference's own schedule: one frame after the other).
              HIP events around every SD trace and around every AO span (clear -> pass 1 ->
@@ -16,7 +16,7 @@ Two timed regions, each K frames between a barrier + torch.cuda.synchronize() pa
                value (Mrays/s)     = dispatched SD rays / SD-kernel time   (whole job)
                active_mrays_per_s  = active SD rays (TMin <= TMax) / SD-kernel time
                ao_frames_per_s     = 1 / AO-span time
-  throughput F frames in flight (--frames-in-flight, default 4): frame i runs on HIP stream
+  throughput K = --steps frames, F in flight (--frames-in-flight, default 4): frame i runs on HIP stream
              i % F with its own frame buffers, frames of different slots overlap (the latency-
              bound SD trace of one frame shares the machine with the VALU-bound passes of
              others; traces are flagged RSD_SD_THROUGHPUT, which librsd may use to pick a walk).
@@ -37,6 +37,15 @@ Multi-GPU (torchrun, one rank per GPU), sharding modes (--shard):
   frame: frames are the independent units -- every rank renders whole frames (its own frame
     stream, BVH + G-buffer replicated), no data-path collective.  Weak scaling.
   gather: round-1 v1 of band -- interleaved bands, whole-map interval all-reduce and SD all-gather.
+
+A plain run does what the headline needs and no more: set-up, warm-up, the two timed regions, the result
+line (metric, value, ms_per_step and the figures the two regions give).  --steps K is the number of timed
+frames of the throughput region (ms_per_step = its wall time / K); the latency region, which gives value,
+times min(K, LATENCY_FRAMES_MAX) frames.  --full adds what takes runs of its own: the instrumented traces
+(traversal counters, roofline, latency floor), the hit-order records, the N > 1 band check and the CPU
+baseline.  --dump-outputs DIR writes what the last timed frame of the throughput region left in its frame
+slot (the AO image, at N = 1 also the SD map) as DIR/<name>.npy, float32; the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -56,6 +65,11 @@ for p in (str(ROOT), str(PKG)):
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 DEFAULT_CONFIG = "suntemple_1080p_q"
+# the latency region (one frame in flight, events around every SD trace) times at most this many frames:
+# its mean settles long before, and a long --steps run spends its time in the region ms_per_step comes from
+LATENCY_FRAMES_MAX = 1000
+# --dump-outputs: an array above this many elements (16 MB as float32) is written as a fixed seeded sample
+DUMP_MAX_ELEMS = 4 << 20
 # committed rocprofv3 passes of the default bench (newest round first)
 PROFILE_DIRS = [ROOT / "profiles" / "round6", ROOT / "profiles" / "round5", ROOT / "profiles" / "round4", ROOT / "profiles" / "round3",
                 ROOT / "profiles" / "round2", ROOT / "profiles" / "round1"]
@@ -104,6 +118,13 @@ def parse():
                     help="per-kernel timing events: hip = fence-free timing events (rsd.timing, default); "
                          "torch = torch.cuda.Event (a system-scope fence per record); off = none in the "
                          "throughput region (the latency region still needs them for value)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the instrumented traces (traversal counters, "
+                         "roofline, latency floor), the hit-order records, the N > 1 band check and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed frames, write what the last frame of the throughput region computed (the AO "
+                         "image, at N = 1 also the SD map) as DIR/<name>.npy in float32; arrays above DUMP_MAX_ELEMS "
+                         "elements as a fixed seeded sample")
     return ap.parse_args()
 
 
@@ -352,11 +373,12 @@ def run_rank(args, grp, local, shared=None):
             rend.gbuffer()
 
     # ---- instrumented traces (untimed): traversal counters for the roofline bytes, for both
-    #      walks, averaged over the poses the timed frames render
+    #      walks, averaged over the poses the timed frames render (--full)
+    full = args.full
     if not poses:
         r.gbuffer()
     cnt_seq, cnt_thr = [], []
-    for i in range(min(args.steps, n_poses)):
+    for i in range(min(args.steps, n_poses) if full else 0):
         pose(r, i)
         for acc, thr in ((cnt_seq, False), (cnt_thr, True)):
             # pass 1 over the whole frame = the exact interval union a band frame all-reduces
@@ -369,8 +391,10 @@ def run_rank(args, grp, local, shared=None):
             else:
                 acc.append(r.sd_trace(counters=True, throughput=thr, band=bw))
     torch.cuda.synchronize()
-    walk_seq, walk_thr = int(cnt_seq[0].walk), int(cnt_thr[0].walk)
-    walk_seq_inst = int(cnt_seq[0].walk_instrumented)
+    walk_seq = walk_thr = walk_seq_inst = None
+    if full:
+        walk_seq, walk_thr = int(cnt_seq[0].walk), int(cnt_thr[0].walk)
+        walk_seq_inst = int(cnt_seq[0].walk_instrumented)
     mean_cnt = lambda cs, f: float(np.mean([getattr(c, f) for c in cs]))  # noqa: E731
     if dist:
         dist.barrier()
@@ -399,7 +423,8 @@ def run_rank(args, grp, local, shared=None):
     else:
         from rsd.timing import TimingEvent as new_ev
     mk_ev = lambda n: [(new_ev(), new_ev()) for _ in range(n)]  # noqa: E731
-    ev_sd, ev_ao = mk_ev(args.steps), mk_ev(args.steps)
+    lat_steps = min(args.steps, LATENCY_FRAMES_MAX)
+    ev_sd, ev_ao = mk_ev(lat_steps), mk_ev(lat_steps)
 
     def run_seq(n, timed_ev=True):
         for i in range(n):
@@ -410,8 +435,8 @@ def run_rank(args, grp, local, shared=None):
             if timed_ev:
                 ev_ao[i][1].record()
 
-    run_seq(args.warmup, timed_ev=False)
-    wall_seq = timed(run_seq, args.steps)
+    run_seq(min(args.warmup, LATENCY_FRAMES_MAX), timed_ev=False)
+    wall_seq = timed(run_seq, lat_steps)
     seq_sd_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_sd]))
     seq_ao_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_ao]))
 
@@ -465,13 +490,17 @@ def run_rank(args, grp, local, shared=None):
     wall_thr = timed(run_thr, args.steps)
     thr_sd_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_thr])) if thr_ev else float("nan")
 
+    if args.dump_outputs and rank == 0:
+        # the last timed frame ran in slot (steps - 1) % F; nothing has touched its buffers since
+        dump_outputs(args.dump_outputs, slots[(args.steps - 1) % F].b, with_sd=world == 1)
+
     if dist:  # per-kernel times: the slowest rank
         seq_sd_ms, seq_ao_ms, thr_sd_ms = dist.reduce([seq_sd_ms, seq_ao_ms, thr_sd_ms], "max")
 
     # N > 1 band frames (untimed): one more frame of the split, checked on rank 0 against the 1-GPU frame of the same
     # pose (rsd_svao_frame on a frame slot of its own) -- every rank's gathered AO image must be those bits
     band_check = None
-    if world > 1 and shard == "band":
+    if full and world > 1 and shard == "band":
         pose(r, 0)
         r.ao.zero_()
         seq.frame()
@@ -490,57 +519,58 @@ def run_rank(args, grp, local, shared=None):
     N = cfg.sd_samples
     # frame mode: every rank renders whole frames; band mode: the ranks share each frame
     units = world if shard == "frame" else 1
-    rays_active = mean_cnt(cnt_seq, "rays_active")
-    # the segment entry grid's lookups: one 16-B hash slot + 32 B per frontier item tested
-    entry_bytes = 16 * mean_cnt(cnt_seq, "entry_lookups") + 32 * mean_cnt(cnt_seq, "entry_items")
-    if dist and shard != "frame":  # counters are per band: the frame's totals
-        rays_active, nodes_seq, tris_seq, entry_bytes = dist.reduce(
-            [rays_active, mean_cnt(cnt_seq, "nodes_visited"), mean_cnt(cnt_seq, "tris_tested"), entry_bytes], "sum")
-    else:
-        nodes_seq, tris_seq = mean_cnt(cnt_seq, "nodes_visited"), mean_cnt(cnt_seq, "tris_tested")
     value = units * rays / (seq_sd_ms * 1e-3) / 1e6
-    # B_ray = 16 (linearZ bilinear) + 8 (rayMin+rayMax) + 4N (store) + node bytes + 48 n_tri
-    # (+ the entry grid's lookups, which replace the top of the walk);
-    # librsd's nodes are 4-wide (128 B per visit = two of SURVEY's 64-B BVH2 nodes).  Per launch =
-    # per frame (band mode: the whole frame's bytes over the slowest rank's trace time).
-    # (the store term counts only the texels written: clean tiles, --clean-tiles, are not rewritten)
-    texels_clean = mean_cnt(cnt_seq, "texels_clean")
-    if dist and shard != "frame":
-        texels_clean = dist.reduce([texels_clean], "sum")[0]
-    alg_bytes = rays * (16 + 8) + (rays - texels_clean) * 4 * N + 128 * nodes_seq + 48 * tris_seq + entry_bytes
-    achieved = alg_bytes / (seq_sd_ms * 1e-3) / 1e9
-    kernels_seq = abi.WALK_KERNELS[walk_seq]
-    if r.sd_w * r.sd_h > 2_000_000 and walk_seq != abi.WALK_RASTER:
-        # the full-resolution maps' two-pass setup (sd_trace.hip: sd_classify_kernel + sd_live_kernel above 2 M
-        # texels) in place of the one-pass setup kernel
-        kernels_seq = ("sd_classify_kernel", "sd_live_kernel") + tuple(k for k in kernels_seq if k != "sd_setup_kernel")
-    lat = latency_floor(cnt_seq, seq_sd_ms)
-    if lat.get("latency_floor_us") is not None:
-        # the step clocks come from the instrumented launch, which walks the row or quad walk alone -- for the hybrid
-        # launch (walk 6), the row walk its first blocks run over the longest-first rays
-        lat["latency_walk"] = abi.WALK_NAMES[walk_seq_inst]
-    pmc = args.pmc_csv
-    if pmc is None and not args.scene_file:
-        # the committed passes of this config (tools/config_measure.sh -> profiles/roundN/configs/<config>/),
-        # or of the default config (tools/round_measure.sh -> profiles/roundN/)
-        for d in PROFILE_DIRS:
-            dd = d / "configs" / args.config
-            cands = [[dd / "pmc_fetch_size.csv", dd / "pmc_write_size.csv"]]
-            if args.config == DEFAULT_CONFIG and not poses:
-                cands.append([d / "pmc_fetch_size.csv", d / "pmc_write_size.csv"])
-            cand = next((c for c in cands if all(p.exists() for p in c)), None)
-            if cand:
-                pmc = [str(p) for p in cand]
-                break
-    pmc = [p for p in (pmc or []) if Path(p).exists()]
-    traffic = pmc_traffic(pmc, kernels_seq)
-    valu_csv = next((d / "pmc_sq_valu.csv" for d in PROFILE_DIRS if (d / "pmc_sq_valu.csv").exists()), None)
+    if full:  # the instrumented traces' counters: traversal, roofline, latency floor
+        rays_active = mean_cnt(cnt_seq, "rays_active")
+        # the segment entry grid's lookups: one 16-B hash slot + 32 B per frontier item tested
+        entry_bytes = 16 * mean_cnt(cnt_seq, "entry_lookups") + 32 * mean_cnt(cnt_seq, "entry_items")
+        if dist and shard != "frame":  # counters are per band: the frame's totals
+            rays_active, nodes_seq, tris_seq, entry_bytes = dist.reduce(
+                [rays_active, mean_cnt(cnt_seq, "nodes_visited"), mean_cnt(cnt_seq, "tris_tested"), entry_bytes], "sum")
+        else:
+            nodes_seq, tris_seq = mean_cnt(cnt_seq, "nodes_visited"), mean_cnt(cnt_seq, "tris_tested")
+        # B_ray = 16 (linearZ bilinear) + 8 (rayMin+rayMax) + 4N (store) + node bytes + 48 n_tri
+        # (+ the entry grid's lookups, which replace the top of the walk);
+        # librsd's nodes are 4-wide (128 B per visit = two of SURVEY's 64-B BVH2 nodes).  Per launch =
+        # per frame (band mode: the whole frame's bytes over the slowest rank's trace time).
+        # (the store term counts only the texels written: clean tiles, --clean-tiles, are not rewritten)
+        texels_clean = mean_cnt(cnt_seq, "texels_clean")
+        if dist and shard != "frame":
+            texels_clean = dist.reduce([texels_clean], "sum")[0]
+        alg_bytes = rays * (16 + 8) + (rays - texels_clean) * 4 * N + 128 * nodes_seq + 48 * tris_seq + entry_bytes
+        achieved = alg_bytes / (seq_sd_ms * 1e-3) / 1e9
+        kernels_seq = abi.WALK_KERNELS[walk_seq]
+        if r.sd_w * r.sd_h > 2_000_000 and walk_seq != abi.WALK_RASTER:
+            # the full-resolution maps' two-pass setup (sd_trace.hip: sd_classify_kernel + sd_live_kernel above 2 M
+            # texels) in place of the one-pass setup kernel
+            kernels_seq = ("sd_classify_kernel", "sd_live_kernel") + tuple(k for k in kernels_seq if k != "sd_setup_kernel")
+        lat = latency_floor(cnt_seq, seq_sd_ms)
+        if lat.get("latency_floor_us") is not None:
+            # the step clocks come from the instrumented launch, which walks the row or quad walk alone -- for the hybrid
+            # launch (walk 6), the row walk its first blocks run over the longest-first rays
+            lat["latency_walk"] = abi.WALK_NAMES[walk_seq_inst]
+        pmc = args.pmc_csv
+        if pmc is None and not args.scene_file:
+            # the committed passes of this config (tools/config_measure.sh -> profiles/roundN/configs/<config>/),
+            # or of the default config (tools/round_measure.sh -> profiles/roundN/)
+            for d in PROFILE_DIRS:
+                dd = d / "configs" / args.config
+                cands = [[dd / "pmc_fetch_size.csv", dd / "pmc_write_size.csv"]]
+                if args.config == DEFAULT_CONFIG and not poses:
+                    cands.append([d / "pmc_fetch_size.csv", d / "pmc_write_size.csv"])
+                cand = next((c for c in cands if all(p.exists() for p in c)), None)
+                if cand:
+                    pmc = [str(p) for p in cand]
+                    break
+        pmc = [p for p in (pmc or []) if Path(p).exists()]
+        traffic = pmc_traffic(pmc, kernels_seq)
+        valu_csv = next((d / "pmc_sq_valu.csv" for d in PROFILE_DIRS if (d / "pmc_sq_valu.csv").exists()), None)
 
     # DXR-like any-hit order (rsd_hit_order TRAVERSAL): the same latency region with
     # the traversal-order hit stream -- the mode closest to the reference's DXR semantics
     # (Common.slangh:137-151: the reservoir samples among the hits in traversal order)
     hit_trav = hit_wave = None
-    if world == 1 and args.hit_order_record:
+    if full and world == 1 and args.hit_order_record:
         hit_trav = hit_order_record(r, HaloFrame, new_ev, min(args.steps, 50), min(args.warmup, 5), pose,
                                     rays, rays_active)
         # the wavefront order (round 5): the same stochastic semantics on the row walk's traversal
@@ -553,7 +583,7 @@ def run_rank(args, grp, local, shared=None):
         return
 
     cpu = None
-    if args.cpu_baseline_seconds > 0 and world == 1:
+    if full and args.cpu_baseline_seconds > 0 and world == 1:
         cpu = cpu_baseline(r, scene, args.cpu_baseline_seconds, poses)
 
     frames_thr = args.steps * units
@@ -585,48 +615,52 @@ def run_rank(args, grp, local, shared=None):
                             "latency region; BASELINE.md section 4), summed over ranks",
         "sd_kernel_ms": round(seq_sd_ms, 4),
         "rays_dispatched": rays * units,
-        "active_rays": int(round(rays_active)) * units,
-        "active_mrays_per_s": round(units * rays_active / (seq_sd_ms * 1e-3) / 1e6, 2),
         "ao_frames_per_s": round(units * 1e3 / seq_ao_ms, 2),
         "ao_span_ms": round(seq_ao_ms, 4),
-        "latency": {"ms_per_frame": round(wall_seq / args.steps * 1e3, 4), "frames": args.steps,
-                    "walk": abi.WALK_NAMES[walk_seq],
+        "latency": {"ms_per_frame": round(wall_seq / lat_steps * 1e3, 4), "frames": lat_steps,
                     "note": "one frame in flight; ms_per_frame includes the G-buffer of a camera path, "
                             "ao_span_ms does not"},
         "throughput": {"frames_in_flight": F, "frames": frames_thr, "ms_per_frame": round(wall_thr / args.steps * 1e3, 4),
                        "ao_frames_per_s": round(frames_thr / wall_thr, 2),
                        "frame_mrays_per_s": round(rays * frames_thr / wall_thr / 1e6, 2),
                        "sd_kernel_ms_overlapped": round(thr_sd_ms, 4) if thr_ev else None,
-                       "timing_events": args.timing_events,
-                       "walk": abi.WALK_NAMES[walk_thr]},
-        "traversal": {"nodes_per_ray": round(nodes_seq / rays / units, 3),
-                      "tris_per_ray": round(tris_seq / rays / units, 3),
-                      "nodes_per_active_ray": round(nodes_seq / max(rays_active, 1), 2),
-                      "tris_per_active_ray": round(tris_seq / max(rays_active, 1), 2),
-                      "max_steps_per_ray": int(max(c.max_steps_per_ray for c in cnt_seq))},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "kernel": "rsd_sd_trace = " + " + ".join(kernels_seq),
-                     "alg_bytes_per_launch": int(alg_bytes),
-                     "duration_us": round(seq_sd_ms * 1e3, 2),
-                     "note": "achieved = SURVEY 8(d) algorithmic bytes of one trace / its HIP-event duration in "
-                             "the latency region; traffic = FETCH_SIZE + WRITE_SIZE of the same kernels "
-                             "(per launch, committed rocprofv3 --pmc passes)",
-                     "traffic_source": ", ".join(rel(p) for p in pmc) or None,
-                     **lat},
-        # the frame's largest kernel is pass 1, bound by VALU issue rather than HBM
-        "pass1_roofline": pmc_valu(valu_csv, "svao_pass1_kernel") if valu_csv and args.config == DEFAULT_CONFIG and not args.scene_file
-        else None,
+                       "timing_events": args.timing_events},
         "exchange_bytes_per_frame": dict(seq.bytes_per_frame(), dense_halo_equivalent=seq.dense_bytes_per_frame(),
                                          final_split_groups=list(seq.gb))
         if shard == "band" and world > 1 else None,
-        "band_check": band_check,
-        "hit_order_traversal": hit_trav,
-        "hit_order_wavefront": hit_wave,
         "bvh_build_s": round(bvh_build_s, 3),
         "bvh_build_threads": int(r.gscene.info.build_threads),
-        "cpu_baseline": cpu,
+        "full": full,
     }
+    if full:
+        line["latency"]["walk"] = abi.WALK_NAMES[walk_seq]
+        line["throughput"]["walk"] = abi.WALK_NAMES[walk_thr]
+        line.update({
+            "active_rays": int(round(rays_active)) * units,
+            "active_mrays_per_s": round(units * rays_active / (seq_sd_ms * 1e-3) / 1e6, 2),
+            "traversal": {"nodes_per_ray": round(nodes_seq / rays / units, 3),
+                          "tris_per_ray": round(tris_seq / rays / units, 3),
+                          "nodes_per_active_ray": round(nodes_seq / max(rays_active, 1), 2),
+                          "tris_per_active_ray": round(tris_seq / max(rays_active, 1), 2),
+                          "max_steps_per_ray": int(max(c.max_steps_per_ray for c in cnt_seq))},
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                         "kernel": "rsd_sd_trace = " + " + ".join(kernels_seq),
+                         "alg_bytes_per_launch": int(alg_bytes),
+                         "duration_us": round(seq_sd_ms * 1e3, 2),
+                         "note": "achieved = SURVEY 8(d) algorithmic bytes of one trace / its HIP-event duration in "
+                                 "the latency region; traffic = FETCH_SIZE + WRITE_SIZE of the same kernels "
+                                 "(per launch, committed rocprofv3 --pmc passes)",
+                         "traffic_source": ", ".join(rel(p) for p in pmc) or None,
+                         **lat},
+            # the frame's largest kernel is pass 1, bound by VALU issue rather than HBM
+            "pass1_roofline": pmc_valu(valu_csv, "svao_pass1_kernel") if valu_csv and args.config == DEFAULT_CONFIG and not args.scene_file
+            else None,
+            "band_check": band_check,
+            "hit_order_traversal": hit_trav,
+            "hit_order_wavefront": hit_wave,
+            "cpu_baseline": cpu,
+        })
     if isinstance(grp, ThreadGroup):
         line["n_gpus"] = 1
         line["preflight"] = {"ranks": world, "group": grp.kind,
@@ -637,6 +671,25 @@ def run_rank(args, grp, local, shared=None):
     print(json.dumps(line))
     close_frames([seq] + slots, comms)
     grp.close()
+
+
+def dump_outputs(out_dir, rend, with_sd):
+    """--dump-outputs: the buffers a caller of the timed frame receives, as they stand after its last step -- the AO
+    image of the frame slot `rend` and, when the slot holds the whole map (N = 1), its SD map -- as float32 .npy
+    files.  An array above DUMP_MAX_ELEMS elements is written as the elements at a fixed seeded set of flat
+    indices (ascending), so two runs sample the same places."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {"ao": rend.ao}
+    if with_sd:
+        arrays["sd"] = rend.sd
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_ELEMS))
+            a = a.reshape(-1)[idx]
+        np.save(out / f"{name}.npy", a.astype(np.float32))
 
 
 def close_frames(frames, comms):

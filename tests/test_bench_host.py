@@ -24,6 +24,35 @@ def test_bench_defaults(monkeypatch):
     assert (a.shard, a.frames_in_flight) == ("band", 1)
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    a = _bench(monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "3"]).parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = _bench(monkeypatch, ["--full", "--dump-outputs", "out"]).parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_and_samples_alike(monkeypatch, tmp_path):
+    """--dump-outputs: float32 .npy files; an array above DUMP_MAX_ELEMS is the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    bench = _bench(monkeypatch)
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+
+    class Slot:
+        ao = (torch.arange(30 * 20) % 256).to(torch.uint8).reshape(30, 20)
+        sd = torch.arange(2 * 9 * 31 * 4, dtype=torch.float32).reshape(2, 9, 31, 4) / 7
+
+    bench.dump_outputs(tmp_path / "a", Slot, with_sd=True)
+    bench.dump_outputs(tmp_path / "b", Slot, with_sd=True)
+    bench.dump_outputs(tmp_path / "c", Slot, with_sd=False)
+    ao, sd = np.load(tmp_path / "a" / "ao.npy"), np.load(tmp_path / "a" / "sd.npy")
+    assert ao.dtype == sd.dtype == np.float32
+    assert np.array_equal(ao, Slot.ao.numpy().astype(np.float32))  # small enough: whole
+    assert sd.shape == (1000,) and np.isin(sd, Slot.sd.numpy()).all()
+    assert np.array_equal(sd, np.load(tmp_path / "b" / "sd.npy"))
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["ao.npy"]
+
+
 def test_committed_pmc_passes_parse(monkeypatch):
     bench = _bench(monkeypatch)
     p = ROOT / "profiles" / "round1"

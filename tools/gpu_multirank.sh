@@ -11,11 +11,11 @@ mkdir -p "$OUT"
 export RSD_BENCH_BACKEND=gloo
 for SH in frame band gather; do
   timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 4 --cpu-baseline-seconds 0 --shard $SH \
+    --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 4 --cpu-baseline-seconds 0 --shard $SH \
     > "$OUT/bench_n2_$SH.json" 2> "$OUT/bench_n2_$SH.err" || exit $?
 done
 for N in 2 3; do
   timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-    --master-port 29534 bench.py --gpus $N --steps 6 --warmup 2 --frames-in-flight 1 --cpu-baseline-seconds 0 \
+    --master-port 29534 bench.py --full --gpus $N --steps 6 --warmup 2 --frames-in-flight 1 --cpu-baseline-seconds 0 \
     --config emerald_4k_q > "$OUT/bench_n${N}_4k_band.json" 2> "$OUT/bench_n${N}_4k_band.err" || exit $?
 done
