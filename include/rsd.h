@@ -196,7 +196,8 @@ typedef struct {
                                       1 DualDepth (the second depth layer d_depth2 refines the raster samples,
                                       SVAORaster.ps.slang:69-70, Common.slang:498-505, :555-558) */
     const float* d_depth2;         /* ABI v5: DualDepth: gDepthTex2, linear depth of the second layer
-                                      (DepthPeeling / TemporalDepthPeel), width x height R32F */
+                                      (rsd_depth_peel, the DepthPeeling pass; the reference's other producer,
+                                      TemporalDepthPeel, is not part of librsd), width x height R32F */
 } rsd_svao_params;
 /* SVAO's AO kernel (SVAO::mKernel, a UI dropdown in the reference, SVAO.cpp:615-620):
  *   VAO   volumetric obscurance: visibility = min over the samples of the sphere + halo terms (default);
@@ -321,6 +322,17 @@ rsd_status rsd_gbuffer(rsd_scene* scene, const rsd_camera* cam, uint32_t width, 
  * view space, 2x8 octahedral). */
 rsd_status rsd_gbuffer_raster(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
                               uint32_t cull_mode, float* d_depth, float* d_normal_w, rsd_stream stream);
+/* DepthPeeling (DepthPeeling.3d.slang:16-28, DepthPeeling.cpp:91-115): the next depth layer behind
+ * d_prev_linear_z (linear view depth, width x height R32F), the producer of DualDepth's d_depth2.
+ * Per pixel the primary ray, culling and alpha test of rsd_gbuffer_raster; a hit of linear depth z is
+ * discarded iff z <= prev + min_separation (a NaN sum discards nothing, +inf everything), and the
+ * nearest surviving hit is written:
+ *   linear_out = 0  its non-linear [0,1] depth as GBufferRaster.depth, 1.0 where nothing survives
+ *                   (the DepthPeeling graph pass; LinearizeDepth turns it into d_depth2);
+ *   linear_out = 1  its linear view depth, cam->farZ where nothing survives (d_depth2 directly). */
+rsd_status rsd_depth_peel(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
+                          uint32_t cull_mode, const float* d_prev_linear_z, float min_separation,
+                          uint32_t linear_out, float* d_depth2, rsd_stream stream);
 rsd_status rsd_linearize_depth(const float* d_depth, float* d_linear_z, uint32_t count, float near_z, float far_z,
                                rsd_stream stream);
 rsd_status rsd_compress_normals(const float* d_normal_w, uint16_t* d_packed, uint32_t count,

@@ -6,6 +6,7 @@
 //                                                    mvec when connected (rsd_motion_vectors_raster)
 //   LinearizeDepth        LinearizeDepth.cpp:73-96   rsd_linearize_depth
 //   CompressNormals       CompressNormals.cpp:70-96  rsd_compress_normals (viewSpace, 16 bit)
+//   DepthPeeling          DepthPeeling.cpp:54-115    rsd_depth_peel (DualDepth's second layer)
 //   StochasticDepthMapRT  StochasticDepthMapRT.cpp   rsd_sd_trace            (the hot path)
 //   SVAO                  SVAO.cpp                   rsd_svao_* + a nested "Stochastic Depth"
 //                                                    graph holding StochasticDepthMapRT
@@ -215,6 +216,49 @@ public:
 
 private:
     const SceneRef* scene_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------ DepthPeeling
+// DepthPeeling.cpp:54-65 Properties, :83-89 reflect, :91-115 execute; DepthPeeling.3d.slang:16-28.
+// The next depth layer behind linearZ, non-linear like GBufferRaster.depth: scripts/SVAO.py feeds
+// it through LinearizeDepth0 into SVAO.depth2 (primaryDepthMode DualDepth).
+class DepthPeelingPass : public RenderPass {
+public:
+    explicit DepthPeelingPass(const Properties& p) {
+        props_ = p;
+        cull_ = toRsdCull(enumProp(p, "cullMode", kCullNames, 2));                // DepthPeeling.h:62
+        minSeparation_ = (float)p.getFloat("minSeparationDistance", 0.5);         // DepthPeeling.h:66
+        // the reference's depth-stencil format; stored as R32Float here, like GBufferRaster.depth
+        const std::string fmt = p.getString("depthFormat", "D32Float");           // DepthPeeling.h:65
+        if (fmt != "D32Float") throw Unsupported("DepthPeeling: only depthFormat D32Float is implemented");
+    }
+    Reflection reflect(const CompileData&) override {
+        Reflection r;
+        r.addInput("linearZ", "linearized depth").format = Format::R32Float;
+        r.addOutput("depth2", "next layer of depth (non-linear)").format = Format::R32Float;
+        return r;
+    }
+    void setScene(Context&, const SceneRef* s) override { scene_ = s; }
+    void execute(Context& ctx, const RenderData& rd) override {
+        Texture* in = rd["linearZ"];
+        Texture* out = rd["depth2"];
+        if (!scene_ || !scene_->scene) {  // DepthPeeling.cpp:100-102: the cleared depth buffer
+            if (hipMemsetD32Async((hipDeviceptr_t)out->ptr, 0x3f800000, (size_t)out->width * out->height,
+                                  ctx.stream) != hipSuccess)
+                throw std::runtime_error("DepthPeeling: clear failed");
+            return;
+        }
+        if (in->format != Format::R32Float || in->width != out->width || in->height != out->height)
+            throw std::runtime_error("DepthPeeling: linearZ must be R32Float at the output size");
+        check(rsd_depth_peel(scene_->scene, &scene_->camera, out->width, out->height, cull_, (const float*)in->ptr,
+                             minSeparation_, 0u, (float*)out->ptr, ctx.stream),
+              "DepthPeeling");
+    }
+
+private:
+    const SceneRef* scene_ = nullptr;
+    uint32_t cull_;
+    float minSeparation_;
 };
 
 // ------------------------------------------------------------------------------ StochasticDepthMapRT
@@ -949,6 +993,7 @@ void registerBuiltinPasses(PluginRegistry& r) {
     r.registerClass("GBufferRaster", "depth + face normal G-buffer", factory<GBufferRasterPass>());
     r.registerClass("LinearizeDepth", "non-linear -> linear view depth", factory<LinearizeDepthPass>());
     r.registerClass("CompressNormals", "view-space 2x8 octahedral normals", factory<CompressNormalsPass>());
+    r.registerClass("DepthPeeling", "next depth layer behind a linear depth map", factory<DepthPeelingPass>());
     r.registerClass("StochasticDepthMapRT", "ray-traced stochastic depth map", factory<StochasticDepthMapRTPass>());
     r.registerClass("SVAO", "stochastic-depth volumetric ambient occlusion", factory<SVAOPass>());
     r.registerClass("CrossBilateralBlur", "depth-aware cross bilateral blur", factory<CrossBilateralBlurPass>());

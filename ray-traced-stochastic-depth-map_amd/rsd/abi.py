@@ -184,7 +184,7 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_comm_rccl_available", "rsd_comm_rccl_unique_id", "rsd_comm_rccl_create", "rsd_comm_hub_create", "rsd_comm_hub_release",
            "rsd_comm_local_create", "rsd_comm_null_create", "rsd_comm_release", "rsd_comm_info", "rsd_comm_all_gather", "rsd_comm_exchange",
            "rsd_band_frame_create", "rsd_band_frame_front", "rsd_band_frame_back", "rsd_band_frame_stats",
-           "rsd_band_frame_release", "rsd_band_frame_set_split"]
+           "rsd_band_frame_release", "rsd_band_frame_set_split", "rsd_depth_peel"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -333,6 +333,8 @@ def lib():
                                                     vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp]
         L.rsd_gbuffer_raster.restype = st
         L.rsd_gbuffer_raster.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, vp, vp]
+        L.rsd_depth_peel.restype = st
+        L.rsd_depth_peel.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, f32, u32, vp, vp]
         L.rsd_linearize_depth.restype = st
         L.rsd_linearize_depth.argtypes = [vp, vp, u32, f32, f32, vp]
         L.rsd_compress_normals.restype = st

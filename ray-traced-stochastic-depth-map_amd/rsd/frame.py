@@ -263,7 +263,7 @@ class Renderer:
         self.depth = torch.empty((H, W), dtype=torch.float32, device=dv)
         self.normals = torch.empty((H, W), dtype=torch.int16, device=dv)
         # DualDepth primary mode: the second depth layer (gDepthTex2; DepthPeeling / TemporalDepthPeel in
-        # the reference's graphs -- the caller fills it)
+        # the reference's graphs): depth_peel() fills it from self.depth, or the caller writes its own
         self.depth2 = torch.zeros((H, W), dtype=torch.float32, device=dv) if cfg.primary == abi.DEPTH_DUAL else None
         # SVAO.cpp:307 clears on first use; dualAO: RG8Unorm (bright, dark)
         self.ao = torch.zeros((H, W, 2) if cfg.dual_ao else (H, W), dtype=torch.uint8, device=dv)
@@ -369,6 +369,18 @@ class Renderer:
         abi.check(abi.lib().rsd_gbuffer(self.gscene.h, C.byref(self.cam), self.cfg.fb_w, self.cfg.fb_h,
                                         self.cfg.cull_mode, _ptr(self.depth), _ptr(self.normals), self.stream),
                   "rsd_gbuffer")
+
+    def depth_peel(self, min_separation: float, cull_mode: int | None = None):
+        """Fill self.depth2, the second depth layer of the DualDepth primary mode, from self.depth: per
+        pixel the nearest surface with linear depth > depth + min_separation, farZ where there is none
+        (rsd_depth_peel, the reference's DepthPeeling pass).  cull_mode=None: the config's.  Call it
+        after gbuffer() and before frame()."""
+        if self.cfg.primary != abi.DEPTH_DUAL:
+            raise ValueError("depth_peel() fills depth2, which only FrameConfig(primary=DEPTH_DUAL) allocates")
+        cull = self.cfg.cull_mode if cull_mode is None else cull_mode
+        abi.check(abi.lib().rsd_depth_peel(self.gscene.h, C.byref(self.cam), self.cfg.fb_w, self.cfg.fb_h, cull,
+                                           _ptr(self.depth), float(min_separation), 1, _ptr(self.depth2),
+                                           self.stream), "rsd_depth_peel")
 
     def clear_intervals(self):
         abi.check(abi.lib().rsd_svao_clear_intervals(_ptr(self.ray_min), _ptr(self.ray_max), self.sd_w * self.sd_h,
