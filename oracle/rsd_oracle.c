@@ -1041,24 +1041,31 @@ static int o_any_hit(const osd_params* p, uint32_t N, const int32_t* lutIdx, con
  * restates that definition (librsd csrc/sd_trace.hip sd_trace_ordered_ray, box test
  * csrc/bvh_traverse.h box_hit) over the same tree, so the GPU result is checked bit for bit;
  * the per-hit algorithm is the reference's (o_any_hit). */
-typedef struct { float invd[3], oinvd[3]; } obox_ray;
+typedef struct { float invd[3], olo[3], ohi[3]; } obox_ray;
 
 static void o_box_setup(obox_ray* b, const float o[3], const float d[3])
 {
     for (int i = 0; i < 3; ++i) {
         const float v = fabsf(d[i]) > 1e-20f ? d[i] : copysignf(1e-20f, d[i]); /* axis-parallel rays */
         b->invd[i] = 1.0f / v;
-        b->oinvd[i] = o[i] * b->invd[i];
+        /* a clamped axis (d = 0): the slab widened by e = 1e20 (2^-22 |o| + 1e-10), folded into the subtrahend of its
+         * lo and hi plane, so a plane through the origin's own coordinate is never reached (librsd ray_setup);
+         * every other axis: o / d itself */
+        const float c = o[i] * b->invd[i];
+        const int clamped = !(fabsf(d[i]) > 1e-20f);
+        const float e = fabsf(b->invd[i]) * (fabsf(o[i]) * 2.384185791015625e-07f + 1e-10f);
+        b->olo[i] = !clamped ? c : (b->invd[i] > 0.0f ? c + e : c - e);
+        b->ohi[i] = !clamped ? c : (b->invd[i] > 0.0f ? c - e : c + e);
     }
 }
 
-/* conservative slab test, entry/exit widened by a relative 1e-5 (librsd box_hit) */
+/* conservative slab test, entry/exit widened by a relative 1e-5 (librsd box_hit; a clamped axis: o_box_setup) */
 static int o_box4(const obox_ray* b, float lox, float hix, float loy, float hiy, float loz, float hiz, float tlo,
                   float thi, float* tnear)
 {
-    const float x0 = fmaf(lox, b->invd[0], -b->oinvd[0]), x1 = fmaf(hix, b->invd[0], -b->oinvd[0]);
-    const float y0 = fmaf(loy, b->invd[1], -b->oinvd[1]), y1 = fmaf(hiy, b->invd[1], -b->oinvd[1]);
-    const float z0 = fmaf(loz, b->invd[2], -b->oinvd[2]), z1 = fmaf(hiz, b->invd[2], -b->oinvd[2]);
+    const float x0 = fmaf(lox, b->invd[0], -b->olo[0]), x1 = fmaf(hix, b->invd[0], -b->ohi[0]);
+    const float y0 = fmaf(loy, b->invd[1], -b->olo[1]), y1 = fmaf(hiy, b->invd[1], -b->ohi[1]);
+    const float z0 = fmaf(loz, b->invd[2], -b->olo[2]), z1 = fmaf(hiz, b->invd[2], -b->ohi[2]);
     float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
     float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
     const float m = 1e-5f * (fabsf(tn) + fabsf(tf));

@@ -21,7 +21,7 @@ struct RayCtx {
     f3 o, d;
     int kx, ky, kz;
     float Sx, Sy, Sz;
-    f3 invd, oinvd;
+    f3 invd, oLo, oHi;  // box test: 1 / d, and o / d for the lo and the hi plane (apart on a clamped axis: ray_setup)
 };
 
 __device__ __forceinline__ float comp(f3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
@@ -44,7 +44,25 @@ __device__ __forceinline__ void ray_setup(RayCtx& r, f3 o, f3 d) {
     // box test reciprocal: avoid 0 * inf = NaN for axis-parallel rays
     auto safe = [](float v) { return fabsf(v) > 1e-20f ? v : copysignf(1e-20f, v); };
     r.invd = mk(1.0f / safe(d.x), 1.0f / safe(d.y), 1.0f / safe(d.z));
-    r.oinvd = mk(o.x * r.invd.x, o.y * r.invd.y, o.z * r.invd.z);
+    // box_hit computes a plane's distance as fma(plane, invd, -o * invd).  On a clamped axis (d = 0) a plane through
+    // the origin's own coordinate comes out at distance (plane - o) 1e20 = 0 instead of "never": a box that only
+    // touches the ray's plane would end at t = 0 and be dropped with the hit on its boundary edge.  There the slab
+    // is widened by e = 1e20 (2^-22 |o| + 1e-10): 1e10 at least, beyond every TMax, and four times the rounding of
+    // o * invd.  A box whose plane lies within about 4 floats of the origin's coordinate (or within 1e-10 of it) is
+    // therefore kept as well: false positives only; a box farther off ends up 1e20 |lo - o| - e away and is
+    // rejected as before.  The sign of invd says which plane the ray enters through, so e is folded into the
+    // subtrahends of the lo and the hi plane.  Every other axis keeps o * invd itself: box_hit gives the bits it
+    // always gave.
+    auto planes = [](float o, float d, float invd, float& lo, float& hi) {
+        const float c = o * invd;
+        const bool clamped = !(fabsf(d) > 1e-20f);
+        const float e = fabsf(invd) * (fabsf(o) * 2.384185791015625e-07f + 1e-10f);
+        lo = !clamped ? c : (invd > 0.0f ? c + e : c - e);
+        hi = !clamped ? c : (invd > 0.0f ? c - e : c + e);
+    };
+    planes(o.x, d.x, r.invd.x, r.oLo.x, r.oHi.x);
+    planes(o.y, d.y, r.invd.y, r.oLo.y, r.oHi.y);
+    planes(o.z, d.z, r.invd.z, r.oLo.z, r.oHi.z);
 }
 
 // IntersectionHelpers.slang:109-180 -- bit-identical to the oracle (no contraction).
@@ -92,13 +110,14 @@ __device__ __forceinline__ bool culled(float det, uint32_t flags, uint32_t cull)
     return cull == 1u ? !front : front;
 }
 
-// Conservative slab test: entry/exit widened by a relative 1e-5 so that a node is skipped
-// only if it cannot hold a reported hit in [tlo, thi].
+// Conservative slab test: entry/exit widened by a relative 1e-5 (and the slab of a clamped axis by ray_setup's e) so
+// that a node is skipped only if it cannot hold a reported hit in [tlo, thi].  The oracle restates it bit for bit (o_box4: the traversal and
+// wavefront orders are defined through it).
 __device__ __forceinline__ bool box_hit(const RayCtx& r, float lox, float hix, float loy, float hiy, float loz,
                                         float hiz, float tlo, float thi, float& tnear) {
-    float x0 = fmaf(lox, r.invd.x, -r.oinvd.x), x1 = fmaf(hix, r.invd.x, -r.oinvd.x);
-    float y0 = fmaf(loy, r.invd.y, -r.oinvd.y), y1 = fmaf(hiy, r.invd.y, -r.oinvd.y);
-    float z0 = fmaf(loz, r.invd.z, -r.oinvd.z), z1 = fmaf(hiz, r.invd.z, -r.oinvd.z);
+    float x0 = fmaf(lox, r.invd.x, -r.oLo.x), x1 = fmaf(hix, r.invd.x, -r.oHi.x);
+    float y0 = fmaf(loy, r.invd.y, -r.oLo.y), y1 = fmaf(hiy, r.invd.y, -r.oHi.y);
+    float z0 = fmaf(loz, r.invd.z, -r.oLo.z), z1 = fmaf(hiz, r.invd.z, -r.oHi.z);
     float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
     float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
     float m = 1e-5f * (fabsf(tn) + fabsf(tf));

@@ -42,7 +42,7 @@ static uint32_t fb(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
 struct Ray {
     float o[3], d[3], tmin, tmax;
-    float invd[3], oinvd[3];
+    float invd[3], olo[3], ohi[3];  // csrc/bvh_traverse.h ray_setup: o / d for the lo and the hi plane
     int kx, ky, kz;
     float Sx, Sy, Sz;
 };
@@ -62,15 +62,20 @@ static void setup(Ray& r) {
     for (int k = 0; k < 3; ++k) {
         float v = std::fabs(r.d[k]) > 1e-20f ? r.d[k] : std::copysign(1e-20f, r.d[k]);
         r.invd[k] = 1.0f / v;
-        r.oinvd[k] = r.o[k] * r.invd[k];
+        // a clamped axis (d = 0): the slab widened by e, as the kernels do
+        const float c = r.o[k] * r.invd[k];
+        const bool clamped = !(std::fabs(r.d[k]) > 1e-20f);
+        const float e = std::fabs(r.invd[k]) * (std::fabs(r.o[k]) * 2.384185791015625e-07f + 1e-10f);
+        r.olo[k] = !clamped ? c : (r.invd[k] > 0.0f ? c + e : c - e);
+        r.ohi[k] = !clamped ? c : (r.invd[k] > 0.0f ? c - e : c + e);
     }
 }
 
 static bool box_hit(const Ray& r, const float lo[3], const float hi[3], float tlo, float thi, float& tn) {
     float t0[3], t1[3];
     for (int k = 0; k < 3; ++k) {
-        t0[k] = std::fma(lo[k], r.invd[k], -r.oinvd[k]);
-        t1[k] = std::fma(hi[k], r.invd[k], -r.oinvd[k]);
+        t0[k] = std::fma(lo[k], r.invd[k], -r.olo[k]);
+        t1[k] = std::fma(hi[k], r.invd[k], -r.ohi[k]);
     }
     float n = std::max(std::max(std::min(t0[0], t1[0]), std::min(t0[1], t1[1])), std::min(t0[2], t1[2]));
     float f = std::min(std::min(std::max(t0[0], t1[0]), std::max(t0[1], t1[1])), std::max(t0[2], t1[2]));
