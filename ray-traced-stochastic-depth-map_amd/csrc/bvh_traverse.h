@@ -1,5 +1,6 @@
 // bvh_traverse.h -- BVH traversal primitives shared by librsd's ray kernels (the SD trace,
-// the primary-visibility G-buffer and the Raytraced secondary mode of SVAO pass 2).
+// the primary-visibility G-buffer, the depth peel and the Raytraced secondary mode of SVAO
+// pass 2), and walk_lane, the one-ray-per-lane walk of the last three.
 //
 // Reference: IntersectionHelpers.slang:109-180 (watertight triangle test), the DXR triangle
 // culling of the instance flags (Scene.cpp:3446-3452), Camera.slang:46-90 (pinhole rays).
@@ -10,6 +11,9 @@
 #include "alpha_test.h"
 
 namespace rsd {
+
+// __forceinline__ spelled for a lambda's call operator
+#define RSD_INLINE_LAMBDA __attribute__((always_inline))
 
 constexpr int kTile = 8;               // 8x8 texels per wave
 constexpr uint32_t kQueueParts = 32;   // live-ray queue partitions (counter sharding)
@@ -131,32 +135,6 @@ __device__ __forceinline__ bool key_less(float ta, uint32_t pa, float tb, uint32
     return ta < tb || (ta == tb && pa < pb);
 }
 
-template <int K>
-struct KList {
-    float t[K];
-    uint32_t p[K];
-    uint32_t l[K];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int j = 0; j < K; ++j) { t[j] = INFINITY; p[j] = 0xffffffffu; l[j] = 0u; }
-    }
-    // insert keeping ascending (t, prim) order; the largest key falls off the end
-    __device__ __forceinline__ void insert(float nt, uint32_t np, uint32_t nl) {
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const bool lt = key_less(nt, np, t[j], p[j]);
-            const float tt = t[j];
-            const uint32_t pp = p[j], ll = l[j];
-            t[j] = lt ? nt : tt;
-            p[j] = lt ? np : pp;
-            l[j] = lt ? nl : ll;
-            nt = lt ? tt : nt;
-            np = lt ? pp : np;
-            nl = lt ? ll : nl;
-        }
-    }
-};
-
 struct TraceStats {
     uint32_t nodes, tris, leaves;
 };
@@ -181,25 +159,57 @@ constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kOffMask = 0x1fffffffu;
 constexpr uint32_t kNoItem = 0xffffffffu;
 
-// Collects the K smallest keys (t, prim) with tmin <= t <= tmax, key > (lbT, lbP) when
-// useLB, culling applied.  Returns the number of keys found (<= K).  Children are visited
-// nearest-first; the others go to a per-lane LDS stack with their entry distance, and a
-// popped item is dropped without a fetch once the k-th key is nearer than its box.
-// alphaOn: alpha-masked triangles that fail the alpha test at LOD 0 are ignored
-// (closest hit with IgnoreHit in the any-hit shader, GBufferRaster useAlphaTest).
-template <int K>
-__device__ __forceinline__ int trace_knearest(const float4* __restrict__ bvh, uint32_t triOff, const RayCtx& r,
-                                              float tmin, float tmax, uint32_t cull, bool useLB, float lbT,
-                                              uint32_t lbP, KList<K>& kl, uint32_t* __restrict__ ldsItem,
-                                              float* __restrict__ ldsT, TraceStats& st, bool alphaOn,
-                                              const AlphaData& alpha) {
-    kl.clear();
+__device__ __forceinline__ uint32_t make_item(uint32_t ref, uint32_t cnt, uint32_t triOff) {
+    return cnt ? (kLeafBit | ((cnt - 1u) << 29) | (triOff + 3u * ref)) : 8u * ref;
+}
+
+// The per-lane stack of walk_lane: (item, entry distance) pairs, the first kLdsStack of them in the
+// lane's column of two LDS arrays of kLdsStack x kBlock words (entry i at [i * kBlock]), the others
+// in two private arrays of kStackTotal - kLdsStack words.  The private arrays are not members: their
+// variable indices would keep a struct that held them in private memory as a whole, sp included.
+struct LaneStack {
+    uint32_t* ldsItem;
+    float* ldsT;
+    uint32_t* spillItem;
+    float* spillT;
+    int sp;
+    __device__ __forceinline__ void push(uint32_t item, float t) {
+        if (sp < kLdsStack) { ldsItem[sp * kBlock] = item; ldsT[sp * kBlock] = t; }
+        else { spillItem[sp - kLdsStack] = item; spillT[sp - kLdsStack] = t; }
+        ++sp;
+    }
+    // the topmost item whose entry distance is <= thi (those above it are dropped), or kNoItem
+    __device__ __forceinline__ uint32_t pop_within(float thi) {
+        while (sp > 0) {
+            --sp;
+            const uint32_t it = sp < kLdsStack ? ldsItem[sp * kBlock] : spillItem[sp - kLdsStack];
+            const float tt = sp < kLdsStack ? ldsT[sp * kBlock] : spillT[sp - kLdsStack];
+            if (tt <= thi) return it;
+        }
+        return kNoItem;
+    }
+};
+
+// One ray per lane through the whole BVH, for the kernels whose lanes walk on their own (the G-buffer,
+// the depth peel; svao_rt.hip's trace_ao restates it).  Children whose box meets [tlo, far()] are
+// visited nearest-first; the others wait on the stack with their entry distance, and a popped item is
+// dropped without a fetch once far() is nearer than its box.
+//   ldsItem, ldsT   the lane's columns of the LDS part of its stack (LaneStack).
+//   far()   the caller's current upper bound, read at a node before its box tests and before popping.
+//   hit(tri, t, bu, bv, det, v0, v1, v2)   every leaf triangle that intersect_tri accepts, in leaf
+//           order; tri = index of its record in the triangle array.  The range test, culling, the key
+//           comparison, the alpha test and the caller's state are the functor's.
+//   CLAMP_KEYS   children are ordered and stacked by fmaxf(entry distance, tlo) instead of the entry
+//           distance: with a lower bound inside the scene, a box the ray is already in at tlo is as
+//           near as any other such box.
+// far and hit are lambdas marked RSD_INLINE_LAMBDA.
+template <bool CLAMP_KEYS, class Far, class Hit>
+__device__ __forceinline__ void walk_lane(const float4* __restrict__ bvh, uint32_t triOff, const RayCtx& r, float tlo,
+                                          uint32_t* __restrict__ ldsItem, float* __restrict__ ldsT, Far far, Hit hit) {
     uint32_t spillItem[kStackTotal - kLdsStack];
     float spillT[kStackTotal - kLdsStack];
-    int sp = 0;
-    int found = 0;
+    LaneStack stack{ldsItem, ldsT, spillItem, spillT, 0};
     uint32_t item = 0;  // root node
-    const float tlo = useLB ? fmaxf(tmin, lbT) : tmin;
     while (true) {
         const float4* p = bvh + (item & kOffMask);
         float4 q[12];
@@ -212,23 +222,12 @@ __device__ __forceinline__ int trace_knearest(const float4* __restrict__ bvh, ui
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if ((uint32_t)j >= cnt) continue;
-                st.tris++;
                 float t, bu, bv, det;
                 if (!intersect_tri(r, q[3 * j], q[3 * j + 1], q[3 * j + 2], t, bu, bv, det)) continue;
-                if (!(t >= tmin && t <= tmax)) continue;
-                const uint32_t prim = __float_as_uint(q[3 * j].w);
-                if (culled(det, __float_as_uint(q[3 * j + 1].w), cull)) continue;
-                if (useLB && !key_less(lbT, lbP, t, prim)) continue;
-                if (!key_less(t, prim, kl.t[K - 1], kl.p[K - 1])) continue;
-                if (alphaOn && (__float_as_uint(q[3 * j + 1].w) & 4u) &&
-                    alpha_test_fails(alpha, prim, q[3 * j], q[3 * j + 1], q[3 * j + 2], bu, bv, false, t, r.d))
-                    continue;
-                kl.insert(t, prim, first + (uint32_t)j);
-                found = found < K ? found + 1 : K;
+                hit(first + (uint32_t)j, t, bu, bv, det, q[3 * j], q[3 * j + 1], q[3 * j + 2]);
             }
         } else {
-            st.nodes++;
-            const float thi = fminf(tmax, kl.t[K - 1]);
+            const float thi = far();
             const uint4 rf = make_uint4(__float_as_uint(q[6].x), __float_as_uint(q[6].y), __float_as_uint(q[6].z),
                                         __float_as_uint(q[6].w));
             const uint4 ct = make_uint4(__float_as_uint(q[7].x), __float_as_uint(q[7].y), __float_as_uint(q[7].z),
@@ -238,53 +237,56 @@ __device__ __forceinline__ int trace_knearest(const float4* __restrict__ bvh, ui
             bool h1 = rf.y != kNoItem && box_hit(r, q[0].y, q[1].y, q[2].y, q[3].y, q[4].y, q[5].y, tlo, thi, k1);
             bool h2 = rf.z != kNoItem && box_hit(r, q[0].z, q[1].z, q[2].z, q[3].z, q[4].z, q[5].z, tlo, thi, k2);
             bool h3 = rf.w != kNoItem && box_hit(r, q[0].w, q[1].w, q[2].w, q[3].w, q[4].w, q[5].w, tlo, thi, k3);
-            auto mkitem = [&](uint32_t ref, uint32_t cnt) {
-                return cnt ? (kLeafBit | ((cnt - 1u) << 29) | (triOff + 3u * ref)) : 8u * ref;
-            };
-            uint32_t c0 = h0 ? mkitem(rf.x, ct.x) : kNoItem, c1 = h1 ? mkitem(rf.y, ct.y) : kNoItem;
-            uint32_t c2 = h2 ? mkitem(rf.z, ct.z) : kNoItem, c3 = h3 ? mkitem(rf.w, ct.w) : kNoItem;
-            k0 = h0 ? k0 : INFINITY;
-            k1 = h1 ? k1 : INFINITY;
-            k2 = h2 ? k2 : INFINITY;
-            k3 = h3 ? k3 : INFINITY;
+            uint32_t c0 = h0 ? make_item(rf.x, ct.x, triOff) : kNoItem;
+            uint32_t c1 = h1 ? make_item(rf.y, ct.y, triOff) : kNoItem;
+            uint32_t c2 = h2 ? make_item(rf.z, ct.z, triOff) : kNoItem;
+            uint32_t c3 = h3 ? make_item(rf.w, ct.w, triOff) : kNoItem;
+            k0 = h0 ? (CLAMP_KEYS ? fmaxf(k0, tlo) : k0) : INFINITY;
+            k1 = h1 ? (CLAMP_KEYS ? fmaxf(k1, tlo) : k1) : INFINITY;
+            k2 = h2 ? (CLAMP_KEYS ? fmaxf(k2, tlo) : k2) : INFINITY;
+            k3 = h3 ? (CLAMP_KEYS ? fmaxf(k3, tlo) : k3) : INFINITY;
             cswap(k0, c0, k1, c1);
             cswap(k2, c2, k3, c3);
             cswap(k0, c0, k2, c2);
             cswap(k1, c1, k3, c3);
             cswap(k1, c1, k2, c2);
-#define RSD_PUSH(c, k)                                                 \
-    if ((c) != kNoItem) {                                              \
-        if (sp < kLdsStack) { ldsItem[sp * kBlock] = (c); ldsT[sp * kBlock] = (k); } \
-        else { spillItem[sp - kLdsStack] = (c); spillT[sp - kLdsStack] = (k); }      \
-        ++sp;                                                          \
-    }
-            RSD_PUSH(c3, k3)
-            RSD_PUSH(c2, k2)
-            RSD_PUSH(c1, k1)
-#undef RSD_PUSH
+            if (c3 != kNoItem) stack.push(c3, k3);
+            if (c2 != kNoItem) stack.push(c2, k2);
+            if (c1 != kNoItem) stack.push(c1, k1);
             next = c0;
         }
         if (next == kNoItem) {
-            const float thi = fminf(tmax, kl.t[K - 1]);
-            while (sp > 0) {
-                --sp;
-                const uint32_t it = sp < kLdsStack ? ldsItem[sp * kBlock] : spillItem[sp - kLdsStack];
-                const float tt = sp < kLdsStack ? ldsT[sp * kBlock] : spillT[sp - kLdsStack];
-                if (tt <= thi) { next = it; break; }
-            }
+            next = stack.pop_within(far());
             if (next == kNoItem) break;
         }
         item = next;
     }
-    return found;
 }
-
 
 __device__ __forceinline__ f3 cam_dir(const rsd_camera& c, float px, float py) {
     const float ndcx = 2.0f * px + -1.0f;
     const float ndcy = -2.0f * py + 1.0f;
     return mk(ndcx * c.U[0] + ndcy * c.V[0] + c.W[0], ndcx * c.U[1] + ndcy * c.V[1] + c.W[1],
               ndcx * c.U[2] + ndcy * c.V[2] + c.W[2]);
+}
+
+// The primary ray through the centre of pixel (x, y) of a W x H image, camera jitter applied
+// (Camera.slang:46-59): unit direction d, cosT = its cosine to the view axis, and the camera's
+// [nearZ, farZ] as the ray's parameter interval.
+__device__ __forceinline__ void primary_ray(const rsd_camera& c, int x, int y, int W, int H, f3& d, float& cosT,
+                                            float& tmin, float& tmax) {
+    const f3 wn = normalize(mk(c.W[0], c.W[1], c.W[2]));
+    d = normalize(cam_dir(c, ((float)x + 0.5f) / (float)W + -c.jitterX, ((float)y + 0.5f) / (float)H + c.jitterY));
+    cosT = dot(wn, d);
+    const float invCos = 1.0f / cosT;
+    tmin = c.nearZ * invCos;
+    tmax = c.farZ * invCos;
+}
+
+// D3D-style [0,1] depth of a right-handed perspective, as GBufferRaster.depth:
+// far (z - near) / (z (far - near))
+__device__ __forceinline__ float raster_depth(const rsd_camera& c, float zlin) {
+    return c.farZ * (zlin - c.nearZ) / (zlin * (c.farZ - c.nearZ));
 }
 
 }  // namespace rsd

@@ -3,7 +3,7 @@
 //   GBufferRaster.depth (non-linear D32 depth) + GBufferRaster.faceNormalW
 //     -> LinearizeDepth.linearDepth (Linearize.ps.slang)
 //     -> CompressNormals.normalOut (CompressNormals.ps.slang, viewSpace + use16Bit)
-// GBufferRaster itself is the closest-hit traversal of sd_trace.hip (rsd_gbuffer_raster);
+// GBufferRaster itself is the closest-hit traversal of gbuffer.hip (rsd_gbuffer_raster);
 // the two converters are elementwise kernels here.
 #include "rsd_device.h"
 #include "rsd_internal.h"

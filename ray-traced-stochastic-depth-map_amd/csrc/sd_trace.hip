@@ -1,6 +1,5 @@
 // sd_trace.hip -- the Ray-SD hot path on gfx950: BVH2 k-nearest any-hit traversal
-// that fills the stochastic depth map, plus the primary-visibility (G-buffer) kernel
-// built on the same traversal.
+// that fills the stochastic depth map.
 //
 // Reference: StochasticDepthMapRT.rt.slang:39-105 (rayGen / anyHit),
 //            Common.slangh:65-92 (initRayDesc), :102-254 (algorithm),
@@ -538,7 +537,7 @@ __device__ __forceinline__ int trace_knearest_quad(const float4* __restrict__ bv
             float tn;
             const bool hit = ref != kNoItem && box_hit(r, lox, hix, loy, hiy, loz, hiz, tlo, thi, tn);
             float k = hit ? tn : INFINITY;
-            uint32_t it = hit ? (cnt ? (kLeafBit | ((cnt - 1u) << 29) | (triOff + 3u * ref)) : 8u * ref) : kNoItem;
+            uint32_t it = hit ? make_item(ref, cnt, triOff) : kNoItem;
             const int m = __popc((uint32_t)(__ballot(hit) >> quadBase) & 0xfu);
             // sorting network (0,1)(2,3) (0,2)(1,3) (1,2) across the quad
             quad_cx<kDppXor1>(k, it, (q & 1) == 0);
@@ -1214,7 +1213,7 @@ __device__ __forceinline__ void sd_trace_ordered_ray(const SDArgs& a, f3 d, floa
             float tn;
             const bool hit = ref != kNoItem && box_hit(r, lox, hix, loy, hiy, loz, hiz, TMin, tCur, tn);
             float k = hit ? tn : INFINITY;
-            uint32_t it = hit ? (ccnt ? (kLeafBit | ((ccnt - 1u) << 29) | (a.triOff + 3u * ref)) : 8u * ref) : kNoItem;
+            uint32_t it = hit ? make_item(ref, ccnt, a.triOff) : kNoItem;
             const int m = __popc((uint32_t)(__ballot(hit) >> quadBase) & 0xfu);
             // sorting network (0,1)(2,3) (0,2)(1,3) (1,2): a pair swaps only if strictly out of order
             quad_cx<kDppXor1>(k, it, (q & 1) == 0);
@@ -1821,8 +1820,7 @@ __device__ __forceinline__ void sd_trace_row_body(const SDArgs& a, const float4*
                 const bool h = rf[j] != kNoItem && box_hit(r, lox[j], hix[j], loy[j], hiy[j], loz[j], hiz[j], tlo,
                                                           thi, tn);
                 ck[j] = h ? tn : INFINITY;
-                ci[j] = h ? (cn[j] ? (kLeafBit | ((cn[j] - 1u) << 29) | (a.triOff + 3u * rf[j])) : 8u * rf[j])
-                          : kNoItem;
+                ci[j] = h ? make_item(rf[j], cn[j], a.triOff) : kNoItem;
                 nc += h;
             }
             // ascending entry distance; misses (INF) sort last
@@ -2189,8 +2187,7 @@ __global__ void __launch_bounds__(kBlock) sd_trace_wavefront_kernel(SDArgs a, co
                 const bool h = rf[j] != kNoItem && box_hit(r, lox[j], hix[j], loy[j], hiy[j], loz[j], hiz[j], TMin,
                                                           thi0, tn);
                 ck[j] = h ? tn : INFINITY;
-                ci[j] = h ? (cn[j] ? (kLeafBit | ((cn[j] - 1u) << 29) | (a.triOff + 3u * rf[j])) : 8u * rf[j])
-                          : kNoItem;
+                ci[j] = h ? make_item(rf[j], cn[j], a.triOff) : kNoItem;
                 nc += h;
             }
             cswap(ck[0], ci[0], ck[1], ci[1]);
@@ -2342,74 +2339,6 @@ __global__ void __launch_bounds__(kBlock) sd_resolve_row_kernel(SDArgs a, const 
         }
     }
     if (a.counters && l == 0 && delivered) atomicAdd(&a.counters[4], (unsigned long long)delivered);
-}
-
-// ------------------------------------------------------------------------------------
-// Primary visibility: closest (t, prim) hit in [near/cos, far/cos] (Camera.slang:46-59),
-// linear depth = t * cos (LinearizeDepth), view-space face normal packed 2x8
-// (CompressNormals.ps.slang, viewSpace + use16Bit).  Miss: depth = farZ, normal = 0.
-// ------------------------------------------------------------------------------------
-struct GBArgs {
-    const float4* nodes;
-    const float4* tris;
-    uint32_t triOff;
-    rsd_camera cam;
-    int W, H;
-    uint32_t cull;
-    float* z;
-    uint16_t* n;
-    float4* nw;  // raster mode: world face normal (RGBA32F); z then holds non-linear depth
-    uint32_t alphaTest;  // the scene has alpha data: alpha test at LOD 0 (GBufferRaster useAlphaTest)
-    AlphaData alpha;
-};
-
-__global__ void __launch_bounds__(kBlock) gbuffer_kernel(GBArgs a) {
-    __shared__ uint32_t sstack[kLdsStack * kBlock];
-    __shared__ float sstackT[kLdsStack * kBlock];
-    const int lane = threadIdx.x;
-    const int x = blockIdx.x * kTile + (lane & (kTile - 1));
-    const int y = blockIdx.y * kTile + (lane / kTile);
-    if (x >= a.W || y >= a.H) return;
-    const rsd_camera& c = a.cam;
-    const f3 wn = normalize(mk(c.W[0], c.W[1], c.W[2]));
-    const f3 d = normalize(cam_dir(c, ((float)x + 0.5f) / (float)a.W + -c.jitterX,
-                                   ((float)y + 0.5f) / (float)a.H + c.jitterY));
-    const float cosT = dot(wn, d);
-    const float invCos = 1.0f / cosT;
-    RayCtx r;
-    ray_setup(r, mk(c.posW[0], c.posW[1], c.posW[2]), d);
-    KList<1> kl;
-    TraceStats st{0u, 0u, 0u};
-    const int found = trace_knearest<1>(a.nodes, a.triOff, r, c.nearZ * invCos, c.farZ * invCos, a.cull, false,
-                                        0.0f, 0u, kl, &sstack[lane], &sstackT[lane], st, a.alphaTest != 0u, a.alpha);
-    const size_t o = (size_t)y * a.W + x;
-    if (!found) {
-        if (a.nw) {
-            a.z[o] = 1.0f;  // cleared depth
-            a.nw[o] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        } else {
-            a.z[o] = c.farZ;
-            a.n[o] = 0;
-        }
-        return;
-    }
-    const float zlin = kl.t[0] * cosT;
-    const uint32_t ti = kl.l[0];
-    const float4 v0 = a.tris[3 * ti], v1 = a.tris[3 * ti + 1], v2 = a.tris[3 * ti + 2];
-    const f3 e1 = mk(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z);
-    const f3 e2 = mk(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z);
-    const f3 nw = normalize(cross(e1, e2));
-    if (a.nw) {
-        // D3D-style [0,1] depth of a right-handed perspective: far (z - near) / (z (far - near))
-        a.z[o] = c.farZ * (zlin - c.nearZ) / (zlin * (c.farZ - c.nearZ));
-        a.nw[o] = make_float4(nw.x, nw.y, nw.z, 0.0f);
-        return;
-    }
-    a.z[o] = zlin;
-    const float* m = c.viewMat;
-    const f3 nv = mk(m[0] * nw.x + m[1] * nw.y + m[2] * nw.z, m[4] * nw.x + m[5] * nw.y + m[6] * nw.z,
-                     m[8] * nw.x + m[9] * nw.y + m[10] * nw.z);
-    a.n[o] = (uint16_t)encode_normal_2x8(nv);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3098,55 +3027,6 @@ extern "C" rsd_status rsd_sd_trace(rsd_scene* scene, const rsd_camera* cam, cons
                                    rsd_counters* counters, rsd_stream stream) {
     return rsd_sd_trace_band(scene, cam, p, d_linear_z, z_w, z_h, d_ray_min, d_ray_max, d_sd_out, sd_w, sd_h, 0, 1,
                              counters, stream);
-}
-
-extern "C" rsd_status rsd_gbuffer(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
-                                  uint32_t cull_mode, float* d_linear_z, uint16_t* d_normals, rsd_stream stream) {
-    if (!scene || !cam || !d_linear_z || !d_normals || width == 0 || height == 0) {
-        set_error("rsd_gbuffer: null argument or empty extent");
-        return RSD_ERR_INVALID_ARG;
-    }
-    if (cull_mode > 2) {
-        set_error("rsd_gbuffer: cull_mode must be 0, 1 or 2");
-        return RSD_ERR_INVALID_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (scene->triangle_count == 0) {
-        std::vector<float> z((size_t)width * height, cam->farZ);
-        RSD_HIP(hipMemcpyAsync(d_linear_z, z.data(), z.size() * 4, hipMemcpyHostToDevice, s));
-        RSD_HIP(hipMemsetAsync(d_normals, 0, (size_t)width * height * 2, s));
-        RSD_HIP(hipStreamSynchronize(s));
-        return RSD_OK;
-    }
-    GBArgs a{scene->d_nodes, scene->d_tris, scene->tri_offset, *cam, (int)width, (int)height, cull_mode, d_linear_z,
-             d_normals, nullptr, scene->d_alpha ? 1u : 0u, scene->alpha};
-    dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
-    hipLaunchKernelGGL(gbuffer_kernel, grid, dim3(kBlock), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "gbuffer_kernel launch");
-    return RSD_OK;
-}
-
-extern "C" rsd_status rsd_gbuffer_raster(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
-                                         uint32_t cull_mode, float* d_depth, float* d_normal_w, rsd_stream stream) {
-    if (!scene || !cam || !d_depth || !d_normal_w || width == 0 || height == 0 || cull_mode > 2) {
-        set_error("rsd_gbuffer_raster: invalid argument");
-        return RSD_ERR_INVALID_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (scene->triangle_count == 0) {
-        std::vector<float> z((size_t)width * height, 1.0f);
-        RSD_HIP(hipMemcpyAsync(d_depth, z.data(), z.size() * 4, hipMemcpyHostToDevice, s));
-        RSD_HIP(hipMemsetAsync(d_normal_w, 0, (size_t)width * height * 16, s));
-        RSD_HIP(hipStreamSynchronize(s));
-        return RSD_OK;
-    }
-    GBArgs a{scene->d_nodes, scene->d_tris, scene->tri_offset, *cam, (int)width, (int)height, cull_mode, d_depth,
-             nullptr, reinterpret_cast<float4*>(d_normal_w), scene->d_alpha ? 1u : 0u, scene->alpha};
-    dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
-    hipLaunchKernelGGL(gbuffer_kernel, grid, dim3(kBlock), 0, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "gbuffer_kernel launch");
 }
 
 namespace rsd {

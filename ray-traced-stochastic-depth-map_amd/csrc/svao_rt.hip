@@ -50,7 +50,12 @@ struct RtArgs {
     AlphaData alpha;
 };
 
-// The aoAnyHit stream of one AO ray reduced to (A, B), see the file header.
+// The aoAnyHit stream of one AO ray reduced to (A, B), see the file header.  The loop is walk_lane's
+// (bvh_traverse.h: same fetch, box tests, make_item, order of pushes and pops) with the upper bound
+// min(tmax, A), but written out with its own stack code: with LaneStack's push and pop in this kernel,
+// through walk_lane or in this loop, the compiler packs half as many of the triangle test's operations
+// (v_pk_*: 112 instead of 214) and the pass measures 2 % slower ("The per-lane
+// walk").  A change to LaneStack has to be made here as well.
 __device__ __forceinline__ void trace_ao(const float4* __restrict__ bvh, uint32_t triOff, const RayCtx& r, float tmin,
                                          float tmax, uint32_t cull, float tCRS, float tSS, float& A, float& B,
                                          uint32_t* __restrict__ ldsItem, float* __restrict__ ldsT, bool alphaOn,
@@ -100,11 +105,10 @@ __device__ __forceinline__ void trace_ao(const float4* __restrict__ bvh, uint32_
             bool h1 = rf.y != kNoItem && box_hit(r, q[0].y, q[1].y, q[2].y, q[3].y, q[4].y, q[5].y, tmin, thi, k1);
             bool h2 = rf.z != kNoItem && box_hit(r, q[0].z, q[1].z, q[2].z, q[3].z, q[4].z, q[5].z, tmin, thi, k2);
             bool h3 = rf.w != kNoItem && box_hit(r, q[0].w, q[1].w, q[2].w, q[3].w, q[4].w, q[5].w, tmin, thi, k3);
-            auto mkitem = [&](uint32_t ref, uint32_t cnt) {
-                return cnt ? (kLeafBit | ((cnt - 1u) << 29) | (triOff + 3u * ref)) : 8u * ref;
-            };
-            uint32_t c0 = h0 ? mkitem(rf.x, ct.x) : kNoItem, c1 = h1 ? mkitem(rf.y, ct.y) : kNoItem;
-            uint32_t c2 = h2 ? mkitem(rf.z, ct.z) : kNoItem, c3 = h3 ? mkitem(rf.w, ct.w) : kNoItem;
+            uint32_t c0 = h0 ? make_item(rf.x, ct.x, triOff) : kNoItem;
+            uint32_t c1 = h1 ? make_item(rf.y, ct.y, triOff) : kNoItem;
+            uint32_t c2 = h2 ? make_item(rf.z, ct.z, triOff) : kNoItem;
+            uint32_t c3 = h3 ? make_item(rf.w, ct.w, triOff) : kNoItem;
             k0 = h0 ? k0 : INFINITY;
             k1 = h1 ? k1 : INFINITY;
             k2 = h2 ? k2 : INFINITY;
@@ -116,7 +120,7 @@ __device__ __forceinline__ void trace_ao(const float4* __restrict__ bvh, uint32_
             cswap(k1, c1, k2, c2);
 #define RSD_PUSH(c, k)                                                                  \
     if ((c) != kNoItem) {                                                               \
-        if (sp < kLdsStack) { ldsItem[sp * 64] = (c); ldsT[sp * 64] = (k); }            \
+        if (sp < kLdsStack) { ldsItem[sp * kBlock] = (c); ldsT[sp * kBlock] = (k); }    \
         else { spillItem[sp - kLdsStack] = (c); spillT[sp - kLdsStack] = (k); }         \
         ++sp;                                                                           \
     }
@@ -130,8 +134,8 @@ __device__ __forceinline__ void trace_ao(const float4* __restrict__ bvh, uint32_
             const float hi = fminf(tmax, A);
             while (sp > 0) {
                 --sp;
-                const uint32_t it = sp < kLdsStack ? ldsItem[sp * 64] : spillItem[sp - kLdsStack];
-                const float tt = sp < kLdsStack ? ldsT[sp * 64] : spillT[sp - kLdsStack];
+                const uint32_t it = sp < kLdsStack ? ldsItem[sp * kBlock] : spillItem[sp - kLdsStack];
+                const float tt = sp < kLdsStack ? ldsT[sp * kBlock] : spillT[sp - kLdsStack];
                 if (tt <= hi) { next = it; break; }
             }
             if (next == kNoItem) break;
@@ -221,9 +225,10 @@ __device__ __forceinline__ void rt_dir(const RtArgs& ra, const Basic& b, float u
 // non-zero stencil are listed in LDS (grouped per pixel, direction order) and every lane
 // traces one AO ray at a time; each pixel's vis = (vis - p_i) + r_i is then applied in
 // direction order (the per-pixel loop's exact float sequence).
-__global__ void __launch_bounds__(64) svao_pass2_rt_kernel(RtArgs ra) {
-    __shared__ uint32_t sItem[kLdsStack * 64];
-    __shared__ float sT[kLdsStack * 64];
+static_assert(kBlock == 64, "svao_pass2_rt_kernel: one wave of 64 lanes per tile, the LaneStack stride");
+__global__ void __launch_bounds__(kBlock) svao_pass2_rt_kernel(RtArgs ra) {
+    __shared__ uint32_t sItem[kLdsStack * kBlock];  // LaneStack columns
+    __shared__ float sT[kLdsStack * kBlock];
     __shared__ uint32_t sPix[64];                    // slot: local pixel
     __shared__ uint16_t sPair[kMaxDirections * 64];  // slot << 5 | direction
     __shared__ uint16_t sFirst[64];

@@ -11,12 +11,14 @@
  *   number of hits and the first `cap` of them in ascending (t, prim) order as t, prim and t * cosT
  *   (slots beyond the count: t = +inf, prim = 0xffffffff, t * cosT = +inf).
  *
- * stack_model: the nearest-first depth-first walk of trace_knearest<1> (csrc/bvh_traverse.h), the G-buffer's walk,
- *   restated over librsd's exported BVH for the primary ray of every pixel: per pixel the high-water mark of the
- *   stack, and the closest key (t, prim) the walk ends with.  A mark above 16 means the walk left the LDS stack
- *   for the private spill arrays.  The copy in csrc/depth_peel.hip walks the same rays but prunes and orders
- *   children from a lower bound raised by prev: it is this walk only when prev + separation <= 0.  The copy in
- *   csrc/svao_rt.hip walks secondary rays, which the model does not cover.
+ * stack_model: librsd's one per-lane walk, the nearest-first depth-first walk_lane with its LaneStack
+ *   (csrc/bvh_traverse.h), restated over librsd's exported BVH as the G-buffer kernel calls it: the primary ray of
+ *   every pixel, the upper bound min(TMax, closest t), no lower bound beyond TMin.  Per pixel the high-water mark
+ *   of the stack, and the closest key (t, prim) the walk ends with.  A mark above 16 means the walk left the LDS
+ *   stack for the private spill arrays.  The depth peel (csrc/depth_peel.hip) calls the same walk on the same rays
+ *   with a lower bound raised by prev, which prunes children and clamps their sort and stack keys: it is the
+ *   modelled walk only when prev + separation <= 0.  The AO rays (csrc/svao_rt.hip, a written-out copy of the
+ *   loop) walk secondary rays, which the model does not cover.
  *
  * Built by the tests with gcc -O2 -ffp-contract=off -pthread against the oracle's shared library.
  */

@@ -137,7 +137,7 @@ def test_grazing_reciprocal_is_large(oracle, hits_lib, name):
 
 
 def test_slivers_spill_the_stack(oracle, hits_lib):
-    """The modelled depth-first walk of the primary rays (the G-buffer's and the peel's) over librsd's own BVH
+    """The modelled per-lane walk of the primary rays (the G-buffer's and the peel's rays) over librsd's own BVH
     leaves the 16-entry LDS stack on >= 64 rays and stays far below kStackTotal = 96; the walk it models finds
     the brute-force closest hit."""
     from rsd.frame import host_bvh

@@ -321,8 +321,8 @@ def test_depth_peel_separation_lands_on_a_layer(oracle, hits_lib, peel_lib, gpu,
 @pytest.mark.parametrize("kernel", ["vao", "hbao"])
 @pytest.mark.parametrize("name,radius", [("layers", 1.0), ("axis_walls", 1.0), ("slivers", 1.0), ("slivers", 6.0)])
 def test_raytraced_pass2_matches_the_oracle(oracle, gpu, name, radius, kernel):
-    """SVAO pass 2 in the Raytraced secondary mode (its own copy of the per-lane stack), exact numerics; on `slivers`
-    also with AO rays long enough to cross many of the needles' boxes."""
+    """SVAO pass 2 in the Raytraced secondary mode (its written-out copy of the per-lane walk, on secondary rays),
+    exact numerics; on `slivers` also with AO rays long enough to cross many of the needles' boxes."""
     from rsd.frame import Renderer
     abi, c = gpu.abi, gpu.case(name)
     cfg = SA.frame_config(N=4, max_count=8, impl=D, radius=radius, ao_kernel=kernel)

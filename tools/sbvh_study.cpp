@@ -229,6 +229,7 @@ int main(int argc, char** argv) {
                         float tn;
                         const int innerIdx = cnt ? -1 : innerSeen++;
                         if (!box_hit(r, lo, hi, r.tmin, thi, tn)) continue;
+                        // the work-item word: csrc/bvh_traverse.h make_item
                         const uint32_t code = cnt ? (0x80000000u | ((cnt - 1u) << 29) | (triOff + 3u * ref)) : 8u * ref;
                         if ((expand == 1 && !cnt) || (expand == 2 && !cnt && innerIdx < spare[l])) {  // open it now
                             const float* c = base + 4 * (size_t)code;
