@@ -322,6 +322,48 @@ rsd_status rsd_gbuffer(rsd_scene* scene, const rsd_camera* cam, uint32_t width, 
  * view space, 2x8 octahedral). */
 rsd_status rsd_gbuffer_raster(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
                               uint32_t cull_mode, float* d_depth, float* d_normal_w, rsd_stream stream);
+/* rsd_gbuffer_raster plus GBufferRaster.posW (RGBA32F, width x height): (o + d t, 1) on a hit -- o the
+ * camera position, d the normalised primary direction, t the winning hit's parameter, every multiply and
+ * add rounded separately -- and (0, 0, 0, 0) on a miss.  d_depth and d_normal_w get rsd_gbuffer_raster's bits. */
+rsd_status rsd_gbuffer_world(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
+                             uint32_t cull_mode, float* d_depth, float* d_normal_w, float* d_pos_w,
+                             rsd_stream stream);
+
+/* --- RTAO: ray-traced ambient occlusion (RenderPasses/RTAO; the ground truth screen-space AO is judged by) ---
+ * Per pixel of the world-position G-buffer, spp cosine-distributed hemisphere rays about the face normal
+ * (Ray.rt.slang:98-212): origin = posW.xyz + n normal_scale, TMin = 0.001, TMax = maxAORayTHit, the closest
+ * hit with no face culling and the alpha test at LOD 0.  spp = 1 draws the direction from the pass's
+ * 5312-entry RGBA8Snorm sample table by hash(x, y, frame_index); spp > 1 from Falcor's
+ * UniformSampleGenerator(pixel, frame_index).  A pixel with posW.w == 0 gets ambient 1 and
+ * ray_distance maxAORayTHit.  The members mirror RTAO.h / RTAOData.slang (the defaults in brackets). */
+typedef struct {
+    float max_t_hit;                           /* mMaxTHit [1] */
+    float normal_scale;                        /* origin offset along the face normal [0.01] */
+    uint32_t apply_exponential_falloff;        /* [1] */
+    float min_occlusion_cutoff;                /* mMinOcclusionCutoff, in (0, 1) with falloff [0.4] */
+    float exponential_falloff_decay_constant;  /* lambda, > 0 with falloff [2] */
+    float minimum_ambient_illumination;        /* [0.07] */
+    uint32_t spp;                              /* rays per pixel, >= 1 [1] */
+    uint32_t pad;
+} rsd_rtao_params;
+#define RSD_RTAO_SAMPLE_COUNT 5312u
+/* RTAO::genSamplesTexture (RTAO.cpp:208-234): the packed RGBA8Snorm sample table (host only) */
+rsd_status rsd_rtao_sample_table(uint32_t out[RSD_RTAO_SAMPLE_COUNT]);
+/* RTAO.cpp:134-141: maxAORayTHit = falloff ? sqrt(ln(cutoff) / -lambda) max_t_hit : max_t_hit, the rays' TMax
+ * (host only; refuses what rsd_rtao refuses about the parameters) */
+rsd_status rsd_rtao_ray_t_max(const rsd_rtao_params* params, float* out);
+/* d_pos_w / d_face_normal_w: RGBA32F, width x height (rsd_gbuffer_world).  d_ambient / d_ray_distance: R32F.
+ * d_ray_log: NULL, or float4[width * height * spp]: entry (y width + x) spp + i = ray i's traced direction
+ * and its hit parameter, 0 on a miss (zeros for a pixel with posW.w == 0).  A scene without triangles: every
+ * ray misses. */
+rsd_status rsd_rtao(rsd_scene* scene, const rsd_rtao_params* params, uint32_t width, uint32_t height,
+                    const float* d_pos_w, const float* d_face_normal_w, uint32_t frame_index, float* d_ambient,
+                    float* d_ray_distance, float* d_ray_log, rsd_stream stream);
+/* The RTAO graph pass's outputs from rsd_rtao's: ambient as R8Unorm, ray_distance as R16Float (round to
+ * nearest even); either pair of pointers may be NULL. */
+rsd_status rsd_rtao_pack(const float* d_ambient, const float* d_ray_distance, uint32_t count, uint8_t* d_ambient_unorm8,
+                         uint16_t* d_ray_distance_f16, rsd_stream stream);
+
 /* DepthPeeling (DepthPeeling.3d.slang:16-28, DepthPeeling.cpp:91-115): the next depth layer behind
  * d_prev_linear_z (linear view depth, width x height R32F), the producer of DualDepth's d_depth2.
  * Per pixel the primary ray, culling and alpha test of rsd_gbuffer_raster; a hit of linear depth z is

@@ -5,10 +5,12 @@
 // pixel-centre primary ray in [near/cos, far/cos], the triangle culling of culled() and the alpha
 // test at LOD 0 applied (closest hit with IgnoreHit in the any-hit shader).  rsd_gbuffer writes the
 // linear depth t * cos and the view-space face normal packed 2x8 (miss: farZ, 0);
-// rsd_gbuffer_raster the non-linear [0,1] depth and the world face normal (miss: 1, 0).
+// rsd_gbuffer_raster the non-linear [0,1] depth and the world face normal (miss: 1, 0);
+// rsd_gbuffer_world those and the world position (o + d t, 1) of GBufferRaster.posW (miss: 0).
 //
 // The walk is walk_lane (bvh_traverse.h) with the upper bound min(tmax, best t) and no lower bound
 // beyond tmin.
+#include <string>
 #include <vector>
 
 #include "bvh_traverse.h"
@@ -27,6 +29,7 @@ struct GBArgs {
     float* z;
     uint16_t* n;
     float4* nw;  // raster mode: world face normal (RGBA32F); z then holds non-linear depth
+    float4* pw;  // raster mode, or null: world position (RGBA32F, w = 1; miss: 0)
     uint32_t alphaTest;  // the scene has alpha data: alpha test at LOD 0 (GBufferRaster useAlphaTest)
     AlphaData alpha;
 };
@@ -70,6 +73,7 @@ __global__ void __launch_bounds__(kBlock) gbuffer_kernel(GBArgs a) {
         if (a.nw) {
             a.z[o] = 1.0f;  // cleared depth
             a.nw[o] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (a.pw) a.pw[o] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         } else {
             a.z[o] = c.farZ;
             a.n[o] = 0;
@@ -84,6 +88,7 @@ __global__ void __launch_bounds__(kBlock) gbuffer_kernel(GBArgs a) {
     if (a.nw) {
         a.z[o] = raster_depth(c, zlin);
         a.nw[o] = make_float4(nw.x, nw.y, nw.z, 0.0f);
+        if (a.pw) a.pw[o] = make_float4(c.posW[0] + d.x * bestT, c.posW[1] + d.y * bestT, c.posW[2] + d.z * bestT, 1.0f);
         return;
     }
     a.z[o] = zlin;
@@ -116,7 +121,7 @@ extern "C" rsd_status rsd_gbuffer(rsd_scene* scene, const rsd_camera* cam, uint3
         return RSD_OK;
     }
     GBArgs a{scene->d_nodes, scene->d_tris, scene->tri_offset, *cam, (int)width, (int)height, cull_mode, d_linear_z,
-             d_normals, nullptr, scene->d_alpha ? 1u : 0u, scene->alpha};
+             d_normals, nullptr, nullptr, scene->d_alpha ? 1u : 0u, scene->alpha};
     dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
     hipLaunchKernelGGL(gbuffer_kernel, grid, dim3(kBlock), 0, s, a);
     hipError_t e = hipGetLastError();
@@ -124,24 +129,44 @@ extern "C" rsd_status rsd_gbuffer(rsd_scene* scene, const rsd_camera* cam, uint3
     return RSD_OK;
 }
 
-extern "C" rsd_status rsd_gbuffer_raster(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
-                                         uint32_t cull_mode, float* d_depth, float* d_normal_w, rsd_stream stream) {
+namespace {
+rsd_status gbuffer_raster(const char* who, rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
+                          uint32_t cull_mode, float* d_depth, float* d_normal_w, float* d_pos_w, hipStream_t s) {
     if (!scene || !cam || !d_depth || !d_normal_w || width == 0 || height == 0 || cull_mode > 2) {
-        set_error("rsd_gbuffer_raster: invalid argument");
+        set_error(std::string(who) + ": invalid argument");
         return RSD_ERR_INVALID_ARG;
     }
-    hipStream_t s = (hipStream_t)stream;
     if (scene->triangle_count == 0) {
         std::vector<float> z((size_t)width * height, 1.0f);
         RSD_HIP(hipMemcpyAsync(d_depth, z.data(), z.size() * 4, hipMemcpyHostToDevice, s));
         RSD_HIP(hipMemsetAsync(d_normal_w, 0, (size_t)width * height * 16, s));
+        if (d_pos_w) RSD_HIP(hipMemsetAsync(d_pos_w, 0, (size_t)width * height * 16, s));
         RSD_HIP(hipStreamSynchronize(s));
         return RSD_OK;
     }
     GBArgs a{scene->d_nodes, scene->d_tris, scene->tri_offset, *cam, (int)width, (int)height, cull_mode, d_depth,
-             nullptr, reinterpret_cast<float4*>(d_normal_w), scene->d_alpha ? 1u : 0u, scene->alpha};
+             nullptr, reinterpret_cast<float4*>(d_normal_w), reinterpret_cast<float4*>(d_pos_w),
+             scene->d_alpha ? 1u : 0u, scene->alpha};
     dim3 grid((width + kTile - 1) / kTile, (height + kTile - 1) / kTile);
     hipLaunchKernelGGL(gbuffer_kernel, grid, dim3(kBlock), 0, s, a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? RSD_OK : hip_fail(e, "gbuffer_kernel launch");
+}
+}  // namespace
+
+extern "C" rsd_status rsd_gbuffer_raster(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
+                                         uint32_t cull_mode, float* d_depth, float* d_normal_w, rsd_stream stream) {
+    return gbuffer_raster("rsd_gbuffer_raster", scene, cam, width, height, cull_mode, d_depth, d_normal_w, nullptr,
+                          (hipStream_t)stream);
+}
+
+extern "C" rsd_status rsd_gbuffer_world(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
+                                        uint32_t cull_mode, float* d_depth, float* d_normal_w, float* d_pos_w,
+                                        rsd_stream stream) {
+    if (!d_pos_w) {
+        set_error("rsd_gbuffer_world: invalid argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    return gbuffer_raster("rsd_gbuffer_world", scene, cam, width, height, cull_mode, d_depth, d_normal_w, d_pos_w,
+                          (hipStream_t)stream);
 }

@@ -3,10 +3,12 @@
 //
 //   GuardBand             GuardBand.cpp:38-64        dict["guardBand"]
 //   GBufferRaster         GBufferRaster.cpp:86-230   depth + faceNormalW (rsd_gbuffer_raster),
-//                                                    mvec when connected (rsd_motion_vectors_raster)
+//                                                    mvec when connected (rsd_motion_vectors_raster),
+//                                                    posW when connected (rsd_gbuffer_world)
 //   LinearizeDepth        LinearizeDepth.cpp:73-96   rsd_linearize_depth
 //   CompressNormals       CompressNormals.cpp:70-96  rsd_compress_normals (viewSpace, 16 bit)
 //   DepthPeeling          DepthPeeling.cpp:54-115    rsd_depth_peel (DualDepth's second layer)
+//   RTAO                  RTAO.cpp:51-158            rsd_rtao (ray-traced AO, the ground truth)
 //   StochasticDepthMapRT  StochasticDepthMapRT.cpp   rsd_sd_trace            (the hot path)
 //   SVAO                  SVAO.cpp                   rsd_svao_* + a nested "Stochastic Depth"
 //                                                    graph holding StochasticDepthMapRT
@@ -121,6 +123,9 @@ public:
         Field& mv = r.addOutput("mvec", "Motion vector (uv units, RG32F)");
         mv.format = Format::RG32Float;
         mv.optional = true;  // GBuffer.cpp:48: mvec is an optional channel, computed only when read
+        Field& pw = r.addOutput("posW", "Position in world space (xyz, w = 1; background 0)");
+        pw.format = Format::RGBA32Float;
+        pw.optional = true;  // GBuffer.cpp:42: likewise
         return r;
     }
     void setScene(Context&, const SceneRef* s) override {
@@ -131,9 +136,17 @@ public:
         if (!scene_) return;  // GBufferRaster.cpp:157 no scene -> outputs stay cleared
         Texture* d = rd["depth"];
         Texture* n = rd["faceNormalW"];
-        check(rsd_gbuffer_raster(scene_->scene, &scene_->camera, d->width, d->height, cull_, (float*)d->ptr,
-                                 (float*)n->ptr, ctx.stream),
-              "GBufferRaster");
+        if (Texture* pw = rd["posW"]) {  // something reads posW: the same kernel writes it too
+            if (pw->format != Format::RGBA32Float || pw->width != d->width || pw->height != d->height)
+                throw Unsupported("GBufferRaster: posW must be RGBA32Float at the depth size");
+            check(rsd_gbuffer_world(scene_->scene, &scene_->camera, d->width, d->height, cull_, (float*)d->ptr,
+                                    (float*)n->ptr, (float*)pw->ptr, ctx.stream),
+                  "GBufferRaster");
+        } else {
+            check(rsd_gbuffer_raster(scene_->scene, &scene_->camera, d->width, d->height, cull_, (float*)d->ptr,
+                                     (float*)n->ptr, ctx.stream),
+                  "GBufferRaster");
+        }
         // mvec (GBufferRaster.cpp:62 "Motion vector").  Static scene: the camera's motion between this frame and the previous execute (the
         // first frame's previous camera is its own, Camera::beginFrame).
         const rsd_camera prev = hasPrev_ ? prevCam_ : scene_->camera;
@@ -148,7 +161,7 @@ public:
                                         (float*)mv->ptr, ctx.stream),
               "GBufferRaster mvec");
     }
-    // further channels (posW, normW, ...) feed passes outside the hot path
+    // further channels (normW, ...) feed passes outside the hot path
     bool acceptsAnyField() const override { return true; }
 
 private:
@@ -259,6 +272,87 @@ private:
     const SceneRef* scene_ = nullptr;
     uint32_t cull_;
     float minSeparation_;
+};
+
+// ------------------------------------------------------------------------------ RTAO
+// RTAO.cpp:64-72 reflect, :80-158 execute; Ray.rt.slang.  The reference pass takes no properties (its values
+// are GUI members, RTAO.h / RTAOData.slang); librsd accepts them as optional keys with the same defaults --
+// a librsd extension: enabled, maxTHit, normalScale, applyExponentialFalloff, minOcclusionCutoff,
+// exponentialFalloffDecayConstant, minimumAmbientIllumination, spp.
+class RTAOPass : public RenderPass {
+public:
+    explicit RTAOPass(const Properties& p) {
+        props_ = p;
+        enabled_ = p.getBool("enabled", true);
+        prm_.max_t_hit = (float)p.getFloat("maxTHit", 1.0);
+        prm_.normal_scale = (float)p.getFloat("normalScale", 0.01);
+        prm_.apply_exponential_falloff = p.getBool("applyExponentialFalloff", true) ? 1u : 0u;
+        prm_.min_occlusion_cutoff = (float)p.getFloat("minOcclusionCutoff", 0.4);
+        prm_.exponential_falloff_decay_constant = (float)p.getFloat("exponentialFalloffDecayConstant", 2.0);
+        prm_.minimum_ambient_illumination = (float)p.getFloat("minimumAmbientIllumination", 0.07);
+        const int64_t spp = p.getInt("spp", 1);
+        if (spp < 1 || spp > 0xffffffffll) throw std::runtime_error("RTAO: spp must be at least 1");
+        prm_.spp = (uint32_t)spp;
+        float tmax;
+        check(rsd_rtao_ray_t_max(&prm_, &tmax), "RTAO");  // bad values are reported when the pass is created
+    }
+    ~RTAOPass() override { release(); }
+    Reflection reflect(const CompileData&) override {
+        Reflection r;
+        r.addInput("wPos", "world position").format = Format::RGBA32Float;
+        r.addInput("faceNormal", "world space face normals").format = Format::RGBA32Float;
+        r.addOutput("ambient", "ambient map").format = Format::R8Unorm;
+        r.addOutput("rayDistance", "distance of the ambient ray").format = Format::R16Float;
+        return r;
+    }
+    void compile(Context&, const CompileData& cd) override {
+        release();
+        width_ = cd.defaultWidth;
+        height_ = cd.defaultHeight;
+        const size_t px = (size_t)width_ * height_;
+        if (hipMalloc(&ambient_, px * 4) != hipSuccess || hipMalloc(&distance_, px * 4) != hipSuccess) {
+            release();
+            throw std::runtime_error("RTAO: result buffer allocation failed");
+        }
+    }
+    void setScene(Context&, const SceneRef* s) override { scene_ = s; }
+    void execute(Context& ctx, const RenderData& rd) override {
+        if (!scene_ || !scene_->scene) return;  // RTAO.cpp:82
+        Texture* wPos = rd["wPos"];
+        Texture* fn = rd["faceNormal"];
+        Texture* amb = rd["ambient"];
+        Texture* dist = rd["rayDistance"];
+        if (!enabled_) {  // RTAO.cpp:89-93: ambient cleared to 1, rayDistance left as it is
+            if (hipMemsetAsync(amb->ptr, 0xff, amb->bytes(), ctx.stream) != hipSuccess)
+                throw std::runtime_error("RTAO: clear failed");
+            return;
+        }
+        const uint32_t W = amb->width, H = amb->height;
+        for (Texture* t : {wPos, fn})
+            if (t->format != Format::RGBA32Float || t->width != W || t->height != H)
+                throw Unsupported("RTAO: wPos and faceNormal must be RGBA32Float at the output size");
+        if (dist->width != W || dist->height != H || W != width_ || H != height_)
+            throw std::runtime_error("RTAO: the outputs must have the frame size");
+        // RTAO.cpp:149: frameIndex++ on every execute
+        check(rsd_rtao(scene_->scene, &prm_, W, H, (const float*)wPos->ptr, (const float*)fn->ptr, frameIndex_++,
+                       ambient_, distance_, nullptr, ctx.stream),
+              "RTAO");
+        check(rsd_rtao_pack(ambient_, distance_, W * H, (uint8_t*)amb->ptr, (uint16_t*)dist->ptr, ctx.stream),
+              "RTAO outputs");
+    }
+
+private:
+    void release() {
+        (void)hipFree(ambient_);
+        (void)hipFree(distance_);
+        ambient_ = distance_ = nullptr;
+    }
+    const SceneRef* scene_ = nullptr;
+    bool enabled_;
+    rsd_rtao_params prm_{};
+    uint32_t frameIndex_ = 0;
+    uint32_t width_ = 0, height_ = 0;
+    float *ambient_ = nullptr, *distance_ = nullptr;  // rsd_rtao's float32 results, converted into the outputs
 };
 
 // ------------------------------------------------------------------------------ StochasticDepthMapRT
@@ -994,6 +1088,7 @@ void registerBuiltinPasses(PluginRegistry& r) {
     r.registerClass("LinearizeDepth", "non-linear -> linear view depth", factory<LinearizeDepthPass>());
     r.registerClass("CompressNormals", "view-space 2x8 octahedral normals", factory<CompressNormalsPass>());
     r.registerClass("DepthPeeling", "next depth layer behind a linear depth map", factory<DepthPeelingPass>());
+    r.registerClass("RTAO", "ray-traced ambient occlusion (ground truth)", factory<RTAOPass>());
     r.registerClass("StochasticDepthMapRT", "ray-traced stochastic depth map", factory<StochasticDepthMapRTPass>());
     r.registerClass("SVAO", "stochastic-depth volumetric ambient occlusion", factory<SVAOPass>());
     r.registerClass("CrossBilateralBlur", "depth-aware cross bilateral blur", factory<CrossBilateralBlurPass>());

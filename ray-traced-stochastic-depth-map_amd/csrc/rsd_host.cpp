@@ -409,6 +409,7 @@ extern "C" void rsd_scene_release(rsd_scene* s) {
     rsd::release_sd_workspaces(s);
     (void)hipFree(s->d_alpha);
     (void)hipFree(s->d_entry);
+    (void)hipFree(s->d_rtao_table);
     delete s;
 }
 

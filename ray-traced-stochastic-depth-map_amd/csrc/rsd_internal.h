@@ -86,6 +86,7 @@ struct rsd_scene {
     float entry_origin[3] = {0.0f, 0.0f, 0.0f}, entry_extent = 0.0f;
     uint64_t entry_items_off = 0;  // bytes from d_entry to the item array
     double entry_build_ms = 0.0;
+    uint32_t* d_rtao_table = nullptr;  // RTAO's sample table (rtao.hip), uploaded by the first rsd_rtao
 };
 
 namespace rsd {

@@ -98,6 +98,20 @@ NUMERICS_FAST, NUMERICS_EXACT = 0, 1  # rsd.h rsd_numerics
 NUMERICS = {"fast": NUMERICS_FAST, "exact": NUMERICS_EXACT}
 
 
+class RTAOParams(C.Structure):  # rsd_rtao_params; the defaults of RTAO.h / RTAOData.slang
+    _fields_ = [("max_t_hit", C.c_float), ("normal_scale", C.c_float), ("apply_exponential_falloff", C.c_uint32),
+                ("min_occlusion_cutoff", C.c_float), ("exponential_falloff_decay_constant", C.c_float),
+                ("minimum_ambient_illumination", C.c_float), ("spp", C.c_uint32), ("pad", C.c_uint32)]
+
+    def __init__(self, max_t_hit=1.0, normal_scale=0.01, apply_exponential_falloff=True, min_occlusion_cutoff=0.4,
+                 exponential_falloff_decay_constant=2.0, minimum_ambient_illumination=0.07, spp=1):
+        super().__init__(max_t_hit, normal_scale, int(apply_exponential_falloff), min_occlusion_cutoff,
+                         exponential_falloff_decay_constant, minimum_ambient_illumination, spp, 0)
+
+
+RTAO_SAMPLE_COUNT = 5312  # rsd.h RSD_RTAO_SAMPLE_COUNT
+
+
 class HaloRegion(C.Structure):  # rsd_halo_region
     _fields_ = [("row0", C.c_uint32), ("row1", C.c_uint32), ("out", C.c_void_p), ("stride", C.c_uint32),
                 ("period", C.c_uint32), ("count", C.c_void_p)]
@@ -184,7 +198,8 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_comm_rccl_available", "rsd_comm_rccl_unique_id", "rsd_comm_rccl_create", "rsd_comm_hub_create", "rsd_comm_hub_release",
            "rsd_comm_local_create", "rsd_comm_null_create", "rsd_comm_release", "rsd_comm_info", "rsd_comm_all_gather", "rsd_comm_exchange",
            "rsd_band_frame_create", "rsd_band_frame_front", "rsd_band_frame_back", "rsd_band_frame_stats",
-           "rsd_band_frame_release", "rsd_band_frame_set_split", "rsd_depth_peel"]
+           "rsd_band_frame_release", "rsd_band_frame_set_split", "rsd_depth_peel", "rsd_gbuffer_world",
+           "rsd_rtao", "rsd_rtao_sample_table", "rsd_rtao_ray_t_max", "rsd_rtao_pack"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -333,6 +348,16 @@ def lib():
                                                     vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp]
         L.rsd_gbuffer_raster.restype = st
         L.rsd_gbuffer_raster.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, vp, vp]
+        L.rsd_gbuffer_world.restype = st
+        L.rsd_gbuffer_world.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, vp, vp, vp]
+        L.rsd_rtao.restype = st
+        L.rsd_rtao.argtypes = [vp, C.POINTER(RTAOParams), u32, u32, vp, vp, u32, vp, vp, vp, vp]
+        L.rsd_rtao_sample_table.restype = st
+        L.rsd_rtao_sample_table.argtypes = [vp]
+        L.rsd_rtao_ray_t_max.restype = st
+        L.rsd_rtao_ray_t_max.argtypes = [C.POINTER(RTAOParams), C.POINTER(f32)]
+        L.rsd_rtao_pack.restype = st
+        L.rsd_rtao_pack.argtypes = [vp, vp, u32, vp, vp, vp]
         L.rsd_depth_peel.restype = st
         L.rsd_depth_peel.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, f32, u32, vp, vp]
         L.rsd_linearize_depth.restype = st

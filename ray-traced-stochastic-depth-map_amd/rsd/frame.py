@@ -382,6 +382,22 @@ class Renderer:
                                            _ptr(self.depth), float(min_separation), 1, _ptr(self.depth2),
                                            self.stream), "rsd_depth_peel")
 
+    def rtao(self, spp: int = 1, frame_index: int = 0, **params):
+        """Ray-traced ambient occlusion of this renderer's frame (rsd_rtao, the reference's RTAO pass): spp
+        cosine-distributed hemisphere rays per pixel from the world-position G-buffer, which rsd_gbuffer_world
+        renders here with the config's cull mode.  params: abi.RTAOParams members (max_t_hit, normal_scale,
+        apply_exponential_falloff, ...).  Returns (ambient, ray_distance), float32 tensors of the frame size."""
+        t, W, H = self.torch, self.cfg.fb_w, self.cfg.fb_h
+        prm = abi.RTAOParams(spp=spp, **params)
+        f32 = dict(dtype=t.float32, device=self.depth.device)
+        depth, normal_w, pos_w = t.empty((H, W), **f32), t.empty((H, W, 4), **f32), t.empty((H, W, 4), **f32)
+        ambient, ray_distance = t.empty((H, W), **f32), t.empty((H, W), **f32)
+        abi.check(abi.lib().rsd_gbuffer_world(self.gscene.h, C.byref(self.cam), W, H, self.cfg.cull_mode, _ptr(depth),
+                                              _ptr(normal_w), _ptr(pos_w), self.stream), "rsd_gbuffer_world")
+        abi.check(abi.lib().rsd_rtao(self.gscene.h, C.byref(prm), W, H, _ptr(pos_w), _ptr(normal_w), int(frame_index),
+                                     _ptr(ambient), _ptr(ray_distance), None, self.stream), "rsd_rtao")
+        return ambient, ray_distance
+
     def clear_intervals(self):
         abi.check(abi.lib().rsd_svao_clear_intervals(_ptr(self.ray_min), _ptr(self.ray_max), self.sd_w * self.sd_h,
                                                      self.stream), "rsd_svao_clear_intervals")
