@@ -16,6 +16,7 @@
 #include "rsd_oracle.h"
 #include <math.h>
 #include <float.h>
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1676,11 +1677,23 @@ static float o_finalize(const octx* x, float avgAO)
     return o_pow(avgAO, x->d->exponent);
 }
 
-/* Common.slang:164-168 UVToSDPixel */
+/* HLSL int(float): D3D's ftoi rounds towards zero, converts NaN to 0 and saturates out-of-range values
+ * (a C cast of those is undefined; x86 returns INT_MIN for all of them) */
+static int o_ftoi(float v)
+{
+    if (v != v) return 0;
+    if (v >= 2147483648.0f) return INT_MAX;
+    if (v <= -2147483648.0f) return INT_MIN;
+    return (int)v;
+}
+
+/* Common.slang:164-168 UVToSDPixel.  A sample position that is NaN (a pixel at depth 0: posV = 0) lands
+ * on texel sdGuard, ftoi's 0 plus the guard; a saturated one ends below zero (INT_MAX + sdGuard wraps, as
+ * HLSL's int does) and clamps to texel 0. */
 static void o_uv_to_sd_pixel(const ovao* d, const float uv[2], int out[2])
 {
     for (int k = 0; k < 2; ++k) {
-        int px = (int)floorf(uv[k] * d->lowResolution[k]) + d->sdGuard;
+        int px = (int)((uint32_t)o_ftoi(floorf(uv[k] * d->lowResolution[k])) + (uint32_t)d->sdGuard);
         int hi = (int)d->lowResolution[k] + d->sdGuard * 2 - 1;
         out[k] = px < 0 ? 0 : (px > hi ? hi : px);
     }

@@ -1,8 +1,12 @@
-"""Shared test helpers: struct conversion between librsd and the oracle, and the oracle
-side of a whole frame (G-buffer -> pass 1 -> SD trace -> pass 2)."""
+"""Shared test helpers: struct conversion between librsd and the oracle, the oracle side of a whole
+frame (G-buffer -> pass 1 -> SD trace -> pass 2), the SVAO parameter sweep of test_svao_params.py /
+test_gpu_svao_params.py, and the grading of a fast-numerics frame against the exact oracle
+(test_gpu_numerics.py, test_gpu_svao_params.py)."""
 from __future__ import annotations
 
 import ctypes as C
+import json
+import os
 
 import numpy as np
 
@@ -50,3 +54,149 @@ def small_frame_config(visible=(160, 96), guard=16, divisor=2, N=4, max_count=8,
     from rsd.frame import FrameConfig
     return FrameConfig(visible_w=visible[0], visible_h=visible[1], guard_band=guard, divisor=divisor,
                        sd_samples=N, max_count=max_count, implementation=impl, sd_guard_px=64, radius=radius)
+
+
+# ---- the SVAO parameter sweep (test_svao_params.py checks on the oracle alone that every point reaches
+# the branches it is meant to reach; test_gpu_svao_params.py runs the kernels at the same points)
+
+# (exponent, thickness, ssMaxRadius, ssRadiusCutoff, radius): the point every other test runs at ...
+SVAO_DEFAULT_POINT = (2.0, 0.0, 512.0, 6.0, 1.0)
+# ... and the points away from it.  ssMaxRadius = 24 clamps the screen radius of the pixels nearest the
+# camera (basic_init shrinks the pixel's AO radius; sample_init leaves the host-evaluated direction terms)
+SVAO_SWEEP = [
+    (1.5, 0.5, 512.0, 6.0, 1.0),
+    (3.0, 1.0, 24.0, 6.0, 1.0),
+    (0.5, 0.25, 48.0, 12.0, 1.0),
+    (1.0, 0.0, 24.0, 6.0, 4.0),
+    (2.0, 2.0, 512.0, 6.0, 1.0),
+]
+# the sweep points whose ssMaxRadius must clamp a good part of the frame, and leave a good part unclamped
+SVAO_CLAMPED_POINTS = (1, 3)
+SVAO_SMALL_VISIBLE = (160, 96)    # the sweep's frame: guard 16, divisor 2, N = 4 (small_frame_config)
+SVAO_RAGGED_VISIBLE = (200, 120)  # ... and a visible size that is no multiple of the 16 / 32-pixel tiles
+
+
+def svao_point_id(point):
+    return "e{:g}_t{:g}_max{:g}_cut{:g}_r{:g}".format(*point)
+
+
+def svao_point_config(point, visible=SVAO_SMALL_VISIBLE, divisor=2, **kw):
+    """The sweep's small frame at `point`: exponent, thickness and radius travel in the FrameConfig."""
+    import dataclasses
+    exponent, thickness, _, _, radius = point
+    return dataclasses.replace(small_frame_config(visible=visible, guard=16, divisor=divisor, N=4, radius=radius),
+                               exponent=exponent, thickness=thickness, **kw)
+
+
+def set_svao_point(vao, point):
+    """Write a sweep point into a VAOData (librsd's or the oracle's: the same public fields)."""
+    vao.exponent, vao.thickness, vao.ssMaxRadius, vao.ssRadiusCutoff, vao.radius = point
+    return vao
+
+
+def radius_in_pixels(cam, vao, depth):
+    """BasicAOData::Init's screen-space radius of every pixel before the ssMaxRadius clamp
+    (Common.slang:296-303), in float32 operation by operation; a pixel is clamped where it exceeds
+    vao.ssMaxRadius."""
+    f = np.float32
+    z = np.asarray(depth, np.float32)
+    rf = f(vao.radius) * f(cam.focalLength)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        pa = rf / (f(cam.frameWidth) * z) * f(vao.resolution[0])
+        pb = rf / (f(cam.frameHeight) * z) * f(vao.resolution[1])
+        return pa + f(0.5) * (pb - pa)
+
+
+# ---- fast numerics graded against the exact oracle (BASELINE.md section 4)
+
+AO_MAE = 1.0 / 255.0   # BASELINE.md section 4: mean absolute AO error over the visible pixels
+AO_P2 = 2              # ... and |diff| <= 2/255 ...
+AO_P2_FRAC = 0.995     # ... on at least 99.5 % of them
+DECISION_FRAC = 0.01   # stencil pixels / touched SD texels allowed to flip (reported; measured far below)
+
+
+def bits_equal(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+def visible_region(cfg):
+    return slice(cfg.guard_band, cfg.fb_h - cfg.guard_band), slice(cfg.guard_band, cfg.fb_w - cfg.guard_band)
+
+
+def ao_stats(a, b, gv, mask=None):
+    """AO difference in 1/255 units over the visible pixels (both channels with dualAO); mask: a boolean
+    image of the visible region's shape selecting a subset of them."""
+    d = np.abs(a[gv].astype(np.int32) - b[gv].astype(np.int32))
+    if mask is not None:
+        d = d[mask]
+    return {"mae": float(d.mean()) / 255.0, "frac_le2": float((d <= AO_P2).mean()), "max": int(d.max()),
+            "frac_exact": float((d == 0).mean())}
+
+
+def check_ao(s, what):
+    assert s["mae"] <= AO_MAE, (what, s)
+    assert s["frac_le2"] >= AO_P2_FRAC, (what, s)
+
+
+def report(case, **kw):
+    """RSD_NUMERICS_REPORT=<path>: the measured figures of a case, appended there as a JSON line."""
+    path = os.environ.get("RSD_NUMERICS_REPORT")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps(dict(case=case, **kw)) + "\n")
+
+
+def grade(oracle, r, scene, case, detail=None):
+    """One fast frame of renderer r (G-buffer already rendered) graded against the oracle.
+    detail: a dict that receives the GPU frame ("gpu"), the oracle's exact AO of the same G-buffer
+    ("ao") and the visible region ("gv"), for a caller that grades subsets of the pixels as well."""
+    import torch
+    cfg = r.cfg
+    assert r.svp.numerics == 0, "the renderer must run the fast numerics"
+    r.clear_intervals()
+    r.pass1()
+    torch.cuda.synchronize()
+    ao1_g = r.ao.cpu().numpy().copy()
+    r.sd_trace()
+    r.pass2()
+    g = r.numpy()
+    cam, vao = to_oracle(r.cam, oracle.Camera), to_oracle(r.vao, oracle.VAOData)
+    sdp, svp = to_oracle(r.sdp, oracle.SDParams), to_oracle(r.svp, oracle.SVAOParams)
+    osc = oracle.Scene(scene.positions, scene.indices, scene.flags, scene.alpha)
+    gv = visible_region(cfg)
+
+    # the exact frame of the oracle on the same G-buffer
+    ao1, st, rmin, rmax = oracle.svao_pass1(cam, vao, svp, g["depth"], g["normals"], r.sd_w, r.sd_h)
+    sd, _ = oracle.sd_trace(osc, cam, sdp, g["depth"], rmin, rmax, r.sd_w, r.sd_h)
+    ao = oracle.svao_pass2(cam, vao, svp, g["depth"], g["normals"], st, sd, ao1)
+    frame = ao_stats(g["ao"], ao, gv)
+    if detail is not None:
+        detail.update(gpu=g, ao=ao, gv=gv)
+
+    # pass-1 decisions
+    stencil_flip = float((g["stencil"][gv] != st[gv]).mean())
+    touched_g = (g["ray_max"] != 0)
+    touched_o = (rmax != 0)
+    touched_flip = float((touched_g != touched_o).sum() / max(1, touched_o.sum()))
+    both = touched_g & touched_o
+    iv_differ = float(((g["ray_min"] != rmin) | (g["ray_max"] != rmax))[both].mean()) if both.any() else 0.0
+    pass1 = ao_stats(ao1_g, ao1, gv)
+
+    # the SD trace of the GPU's own intervals: exact
+    sd_own, stats = oracle.sd_trace(osc, cam, sdp, g["depth"], g["ray_min"], g["ray_max"], r.sd_w, r.sd_h)
+    assert stats[0] > 0, "no live SD rays: degenerate frame"
+    sd_exact = bits_equal(g["sd"], sd_own)
+
+    # pass 2 on the GPU's own inputs
+    ao_own = oracle.svao_pass2(cam, vao, svp, g["depth"], g["normals"], g["stencil"], g["sd"], ao1_g)
+    pass2 = ao_stats(g["ao"], ao_own, gv)
+
+    report(case, frame_ao=frame, pass1_ao=pass1, pass2_ao_own_inputs=pass2, stencil_flip_frac=stencil_flip,
+           touched_texel_flip_frac=touched_flip, interval_bits_differ_frac=iv_differ, sd_map_exact=sd_exact,
+           live_texels=int(touched_o.sum()), stencilled_px=int((st[gv] != 0).sum()))
+    assert sd_exact, (case, "SD map differs from the oracle's trace of the GPU's own intervals")
+    check_ao(frame, (case, "frame"))
+    check_ao(pass2, (case, "pass 2 on own inputs"))
+    assert stencil_flip <= DECISION_FRAC, (case, stencil_flip)
+    assert touched_flip <= DECISION_FRAC, (case, touched_flip)
+    return frame

@@ -6,7 +6,7 @@ section 4's AO tolerance, at every BASELINE config:
 
   * AO of the whole fast frame vs the oracle's exact frame on the same G-buffer (oracle pass 1 ->
     oracle SD trace -> oracle pass 2): mean absolute error <= 1/255 over the visible pixels and
-    |diff| <= 2/255 on >= 99.5 % of them (the tolerance is written below: AO_MAE, AO_P2, AO_P2_FRAC);
+    |diff| <= 2/255 on >= 99.5 % of them (the tolerance is written in helpers.py: AO_MAE, AO_P2, AO_P2_FRAC);
   * the pass-1 decisions: stencil pixels and touched SD texels (an interval requested or not) that
     differ from the oracle's, as fractions (reported, bounded by DECISION_FRAC);
   * the SD trace stays exact: the GPU's SD map equals the oracle's trace of the GPU's OWN intervals
@@ -16,95 +16,16 @@ section 4's AO tolerance, at every BASELINE config:
 
 RSD_NUMERICS_REPORT=<path>: the measured fractions of every case are appended there as JSON lines
 (DESIGN.md section 2 quotes them)."""
-import json
-import os
-
 import numpy as np
 import pytest
 
-from helpers import to_oracle
+from helpers import AO_P2, to_oracle
+from helpers import ao_stats as _ao_stats, check_ao as _check_ao, grade as _grade, report as _report
 
 pytestmark = pytest.mark.gpu
 
-AO_MAE = 1.0 / 255.0   # BASELINE.md section 4: mean absolute AO error over the visible pixels
-AO_P2 = 2              # ... and |diff| <= 2/255 ...
-AO_P2_FRAC = 0.995     # ... on at least 99.5 % of them
-DECISION_FRAC = 0.01   # stencil pixels / touched SD texels allowed to flip (reported; measured far below)
-
-
-def _bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
-def _ao_stats(a, b, gv):
-    """AO difference in 1/255 units over the visible pixels (both channels with dualAO)."""
-    d = np.abs(a[gv].astype(np.int32) - b[gv].astype(np.int32))
-    return {"mae": float(d.mean()) / 255.0, "frac_le2": float((d <= AO_P2).mean()), "max": int(d.max()),
-            "frac_exact": float((d == 0).mean())}
-
-
-def _check_ao(s, what):
-    assert s["mae"] <= AO_MAE, (what, s)
-    assert s["frac_le2"] >= AO_P2_FRAC, (what, s)
-
-
-def _report(case, **kw):
-    path = os.environ.get("RSD_NUMERICS_REPORT")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(dict(case=case, **kw)) + "\n")
-
-
-def _grade(oracle, r, scene, case):
-    """One fast frame of renderer r (G-buffer already rendered) graded against the oracle."""
-    import torch
-    cfg = r.cfg
-    assert r.svp.numerics == 0, "the renderer must run the fast numerics"
-    r.clear_intervals()
-    r.pass1()
-    torch.cuda.synchronize()
-    ao1_g = r.ao.cpu().numpy().copy()
-    r.sd_trace()
-    r.pass2()
-    g = r.numpy()
-    cam, vao = to_oracle(r.cam, oracle.Camera), to_oracle(r.vao, oracle.VAOData)
-    sdp, svp = to_oracle(r.sdp, oracle.SDParams), to_oracle(r.svp, oracle.SVAOParams)
-    osc = oracle.Scene(scene.positions, scene.indices, scene.flags, scene.alpha)
-    gv = slice(cfg.guard_band, cfg.fb_h - cfg.guard_band), slice(cfg.guard_band, cfg.fb_w - cfg.guard_band)
-
-    # the exact frame of the oracle on the same G-buffer
-    ao1, st, rmin, rmax = oracle.svao_pass1(cam, vao, svp, g["depth"], g["normals"], r.sd_w, r.sd_h)
-    sd, _ = oracle.sd_trace(osc, cam, sdp, g["depth"], rmin, rmax, r.sd_w, r.sd_h)
-    ao = oracle.svao_pass2(cam, vao, svp, g["depth"], g["normals"], st, sd, ao1)
-    frame = _ao_stats(g["ao"], ao, gv)
-
-    # pass-1 decisions
-    stencil_flip = float((g["stencil"][gv] != st[gv]).mean())
-    touched_g = (g["ray_max"] != 0)
-    touched_o = (rmax != 0)
-    touched_flip = float((touched_g != touched_o).sum() / max(1, touched_o.sum()))
-    both = touched_g & touched_o
-    iv_differ = float(((g["ray_min"] != rmin) | (g["ray_max"] != rmax))[both].mean()) if both.any() else 0.0
-    pass1 = _ao_stats(ao1_g, ao1, gv)
-
-    # the SD trace of the GPU's own intervals: exact
-    sd_own, stats = oracle.sd_trace(osc, cam, sdp, g["depth"], g["ray_min"], g["ray_max"], r.sd_w, r.sd_h)
-    assert stats[0] > 0, "no live SD rays: degenerate frame"
-    sd_exact = _bits_equal(g["sd"], sd_own)
-
-    # pass 2 on the GPU's own inputs
-    ao_own = oracle.svao_pass2(cam, vao, svp, g["depth"], g["normals"], g["stencil"], g["sd"], ao1_g)
-    pass2 = _ao_stats(g["ao"], ao_own, gv)
-
-    _report(case, frame_ao=frame, pass1_ao=pass1, pass2_ao_own_inputs=pass2, stencil_flip_frac=stencil_flip,
-            touched_texel_flip_frac=touched_flip, interval_bits_differ_frac=iv_differ, sd_map_exact=sd_exact,
-            live_texels=int(touched_o.sum()), stencilled_px=int((st[gv] != 0).sum()))
-    assert sd_exact, (case, "SD map differs from the oracle's trace of the GPU's own intervals")
-    _check_ao(frame, (case, "frame"))
-    _check_ao(pass2, (case, "pass 2 on own inputs"))
-    assert stencil_flip <= DECISION_FRAC, (case, stencil_flip)
-    assert touched_flip <= DECISION_FRAC, (case, touched_flip)
-    return frame
+# the tolerance (AO_MAE, AO_P2, AO_P2_FRAC, DECISION_FRAC) and the grading of a frame live in
+# tests/helpers.py: test_gpu_svao_params.py grades its frames by the same checks
 
 
 @pytest.mark.timeout(900)
