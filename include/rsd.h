@@ -196,8 +196,8 @@ typedef struct {
                                       1 DualDepth (the second depth layer d_depth2 refines the raster samples,
                                       SVAORaster.ps.slang:69-70, Common.slang:498-505, :555-558) */
     const float* d_depth2;         /* ABI v5: DualDepth: gDepthTex2, linear depth of the second layer
-                                      (rsd_depth_peel, the DepthPeeling pass; the reference's other producer,
-                                      TemporalDepthPeel, is not part of librsd), width x height R32F */
+                                      (rsd_depth_peel, the DepthPeeling pass; or rsd_temporal_depth_peel in
+                                      rsd_graph.h, the TemporalDepthPeel pass), width x height R32F */
 } rsd_svao_params;
 /* SVAO's AO kernel (SVAO::mKernel, a UI dropdown in the reference, SVAO.cpp:615-620):
  *   VAO   volumetric obscurance: visibility = min over the samples of the sphere + halo terms (default);

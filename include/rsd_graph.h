@@ -121,6 +121,19 @@ rsd_status rsd_temporal_ao(const uint8_t* d_ao_in, const float* d_linear_z, cons
                            const uint8_t* d_stable_mask, uint32_t width, uint32_t height, uint32_t guard_band,
                            const rsd_camera* cam, const float prev_view_to_cur_view[16], uint8_t* d_ao_out,
                            uint8_t* d_history_out, rsd_stream stream);
+/* TemporalDepthPeel, Implementation::Iterative (TemporalDepthPeel.cpp:161-270, TemporalDepthPeel.ps.slang:
+ * 319-425): the second depth layer of DualDepth SVAO (rsd_svao_params.d_depth2) without scene access.  Per
+ * pixel, the view ray from linear depth + min_separation to farZ is taken into the previous frame with
+ * cur_view_to_prev_view = prevViewMat * inverse(viewMat), clipped to its screen and bisected (at most
+ * max_iterations steps, 0..256; the pass uses 32) against d_prev_depth2, the previous frame's output (zeros
+ * on the first frame); the best sample returns through prev_view_to_cur_view = viewMat * inverse(prevViewMat).
+ * It is written when it lies > depth + min_separation and < 0.99 farZ; every other pixel gets its linear depth.
+ * Both matrices row-major; all images width x height R32F; d_depth2 must not alias d_prev_depth2 (the caller
+ * copies the output into its history after the call, TemporalDepthPeel.cpp:264).  Exact numerics only. */
+rsd_status rsd_temporal_depth_peel(const float* d_linear_z, const float* d_prev_depth2, uint32_t width,
+                                   uint32_t height, const rsd_camera* cam, const float cur_view_to_prev_view[16],
+                                   const float prev_view_to_cur_view[16], float min_separation,
+                                   int32_t max_iterations, float* d_depth2, rsd_stream stream);
 /* GBufferRaster.mvec for a static scene and a moving camera (librsd definition): the pixel-centre
  * primary hit (from the linear depth) projected with the previous camera, prevUV - uv (RG32F). */
 rsd_status rsd_motion_vectors(const rsd_camera* cam, const rsd_camera* prev_cam, const float* d_linear_z,

@@ -17,6 +17,8 @@
 //   ImageEquation         ImageEquation.cpp          rsd_image_equation_compile / _run
 //   Switch                Switch.cpp                 copy of the selected input
 //   TemporalAO            TemporalAO.cpp             rsd_temporal_ao (enabled = False: copy)
+//   TemporalDepthPeel     TemporalDepthPeel.cpp      rsd_temporal_depth_peel (Iterative; DualDepth's
+//                                                    second layer from the previous frame's)
 //   TAA                   TAA.cpp                    rsd_taa
 //   AOFlickerMask         AOFlickerMask.cpp          rsd_ao_flicker_mask
 //   BinaryDilation        BinaryDilation.cpp         rsd_binary_dilation
@@ -79,6 +81,26 @@ uint32_t defaultNumerics() {
 const SceneRef* requireScene(const SceneRef* s, const std::string& who) {
     if (!s || !s->scene) throw std::runtime_error(who + ": no scene set");
     return s;
+}
+
+// to.viewMat * inverse(from.viewMat), row-major: a view-space point of camera `from` in the view space
+// of camera `to` (TemporalAO.cpp:156, TemporalDepthPeel.cpp:191-194).  The view matrix is rigid, so
+// its inverse is the transposed rotation; evaluated in double and rounded once.
+void viewToView(const rsd_camera& from, const rsd_camera& to, float m[16]) {
+    double inv[16] = {};
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) inv[r * 4 + c] = from.viewMat[c * 4 + r];
+        inv[r * 4 + 3] = -((double)from.viewMat[0 * 4 + r] * from.viewMat[3] +
+                           (double)from.viewMat[1 * 4 + r] * from.viewMat[7] +
+                           (double)from.viewMat[2 * 4 + r] * from.viewMat[11]);
+    }
+    inv[15] = 1.0;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            double acc = 0.0;
+            for (int k = 0; k < 4; ++k) acc += (double)to.viewMat[r * 4 + k] * inv[k * 4 + c];
+            m[r * 4 + c] = (float)acc;
+        }
 }
 
 // ------------------------------------------------------------------------------ stubs
@@ -840,21 +862,8 @@ public:
         const rsd_camera prev = hasPrev_ ? prevCam_ : cur;
         prevCam_ = cur;
         hasPrev_ = true;
-        double inv[16] = {};
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) inv[r * 4 + c] = prev.viewMat[c * 4 + r];
-            inv[r * 4 + 3] = -((double)prev.viewMat[0 * 4 + r] * prev.viewMat[3] +
-                               (double)prev.viewMat[1 * 4 + r] * prev.viewMat[7] +
-                               (double)prev.viewMat[2 * 4 + r] * prev.viewMat[11]);
-        }
-        inv[15] = 1.0;
         float m[16];
-        for (int r = 0; r < 4; ++r)
-            for (int c = 0; c < 4; ++c) {
-                double acc = 0.0;
-                for (int k = 0; k < 4; ++k) acc += (double)cur.viewMat[r * 4 + k] * inv[k * 4 + c];
-                m[r * 4 + c] = (float)acc;
-            }
+        viewToView(prev, cur, m);
         check(rsd_temporal_ao((const uint8_t*)in->ptr, (const float*)z->ptr, (const float*)mv->ptr, prevDepth_,
                               prevAo_, prevHist_, mask ? (const uint8_t*)mask->ptr : nullptr, W, H, (uint32_t)g,
                               &cur, m, (uint8_t*)out->ptr, hist_, ctx.stream),
@@ -882,6 +891,83 @@ private:
     bool hasPrev_ = false;
     float* prevDepth_ = nullptr;
     uint8_t *prevAo_ = nullptr, *prevHist_ = nullptr, *hist_ = nullptr;
+    uint32_t w_ = 0, h_ = 0;
+};
+
+// ------------------------------------------------------------------------------ TemporalDepthPeel
+// TemporalDepthPeel.cpp:61-69 Properties (`minSeparationDistance`; other keys warn), :137-146 reflect,
+// :148-152 compile, :161-270 execute with Implementation::Iterative (TemporalDepthPeel.h:81) and
+// mIterations = 32: rsd_temporal_depth_peel against the previous frame's depth2, kept here
+// (allocated and zeroed on first use or a size change, reset by compile) and refreshed from the
+// output after every frame (:264).  mvec is declared so that the scripts' edge connects; the
+// shader never reads it.  The previous camera is kept like TemporalAO's (first frame: the current).
+class TemporalDepthPeelPass : public RenderPass {
+public:
+    explicit TemporalDepthPeelPass(const Properties& p) {
+        props_ = p;
+        minSeparation_ = (float)p.getFloat("minSeparationDistance", 0.5);  // TemporalDepthPeel.h:77
+        for (auto& [key, value] : p.items())
+            if (key != "minSeparationDistance")  // :68 logWarning
+                std::fprintf(stderr, "[rsd] Unknown field `%s` in a TemporalDepthPeel pass dictionary\n", key.c_str());
+    }
+    ~TemporalDepthPeelPass() override { release(); }
+    Reflection reflect(const CompileData&) override {
+        Reflection r;
+        r.addInput("linearZ", "linear depths").format = Format::R32Float;
+        r.addInput("mvec", "Motion vectors").format = Format::RG32Float;
+        r.addOutput("depth2", "depthOut").format = Format::R32Float;
+        return r;
+    }
+    void compile(Context&, const CompileData&) override { release(); }
+    void setScene(Context&, const SceneRef* s) override {
+        scene_ = s;
+        hasPrev_ = false;
+    }
+    void execute(Context& ctx, const RenderData& rd) override {
+        if (!scene_) return;  // :163
+        Texture* z = rd["linearZ"];
+        Texture* out = rd["depth2"];
+        const uint32_t W = out->width, H = out->height;
+        if (z->format != Format::R32Float || z->width != W || z->height != H)
+            throw std::runtime_error("TemporalDepthPeel: linearZ must be R32Float at the output size");
+        const size_t bytes = (size_t)W * H * 4;
+        if (!prevDepth2_ || W != w_ || H != h_) {  // allocatePrevFrameTexture
+            release();
+            if (hipMalloc(&prevDepth2_, bytes) != hipSuccess) {
+                prevDepth2_ = nullptr;
+                throw std::runtime_error("TemporalDepthPeel: history allocation failed");
+            }
+            w_ = W;
+            h_ = H;
+            if (hipMemsetAsync(prevDepth2_, 0, bytes, ctx.stream) != hipSuccess)
+                throw std::runtime_error("TemporalDepthPeel: history clear failed");
+        }
+        const rsd_camera& cur = scene_->camera;
+        const rsd_camera prev = hasPrev_ ? prevCam_ : cur;
+        prevCam_ = cur;
+        hasPrev_ = true;
+        float curToPrev[16], prevToCur[16];
+        viewToView(cur, prev, curToPrev);  // :193 prevViewMat * inverse(viewMat)
+        viewToView(prev, cur, prevToCur);  // :191 viewMat * inverse(prevViewMat)
+        check(rsd_temporal_depth_peel((const float*)z->ptr, prevDepth2_, W, H, &cur, curToPrev, prevToCur,
+                                      minSeparation_, kIterations, (float*)out->ptr, ctx.stream),
+              "TemporalDepthPeel");
+        if (hipMemcpyAsync(prevDepth2_, out->ptr, bytes, hipMemcpyDeviceToDevice, ctx.stream) != hipSuccess)
+            throw std::runtime_error("TemporalDepthPeel: history copy failed");
+    }
+
+private:
+    static constexpr int32_t kIterations = 32;  // TemporalDepthPeel.h:79 mIterations
+    void release() {
+        (void)hipFree(prevDepth2_);
+        prevDepth2_ = nullptr;
+        w_ = h_ = 0;
+    }
+    float minSeparation_;
+    const SceneRef* scene_ = nullptr;
+    rsd_camera prevCam_{};
+    bool hasPrev_ = false;
+    float* prevDepth2_ = nullptr;
     uint32_t w_ = 0, h_ = 0;
 };
 
@@ -1095,6 +1181,8 @@ void registerBuiltinPasses(PluginRegistry& r) {
     r.registerClass("ImageEquation", "per-pixel formula over up to 4 images", factory<ImageEquationPass>());
     r.registerClass("Switch", "forwards the selected input", factory<SwitchPass>());
     r.registerClass("TemporalAO", "temporal AO accumulation over motion vectors", factory<TemporalAOPass>());
+    r.registerClass("TemporalDepthPeel", "second depth layer reprojected from the previous frame's",
+                    factory<TemporalDepthPeelPass>());
     r.registerClass("TAA", "temporal anti-aliasing (colour-box clamped history)", factory<TAAPass>());
     r.registerClass("AOFlickerMask", "stable-pixel mask from depth and normals", factory<AOFlickerMaskPass>());
     r.registerClass("BinaryDilation", "min / max over a radius-2 gather ring", factory<BinaryDilationPass>());

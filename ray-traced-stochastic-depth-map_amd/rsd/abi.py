@@ -213,7 +213,7 @@ GRAPH_EXPORTS = ["rsd_graph_create", "rsd_graph_destroy", "rsd_graph_create_pass
                  "rsd_cross_bilateral_blur", "rsd_image_equation_compile", "rsd_image_equation_info",
                  "rsd_image_equation_run", "rsd_image_equation_release", "rsd_temporal_ao",
                  "rsd_motion_vectors", "rsd_motion_vectors_raster", "rsd_taa", "rsd_ao_flicker_mask", "rsd_binary_dilation",
-                 "rsd_deinterleave", "rsd_interleave", "rsd_ray_min_max_length"]
+                 "rsd_deinterleave", "rsd_interleave", "rsd_ray_min_max_length", "rsd_temporal_depth_peel"]
 
 FMT_R32F, FMT_RG32F, FMT_RGBA32F, FMT_R16U, FMT_R8U, FMT_R8UNORM, FMT_R32U, FMT_UNKNOWN = range(8)
 FMT_R16F, FMT_RG16F, FMT_RGBA16F, FMT_RG8UNORM = 8, 9, 10, 11
@@ -392,6 +392,8 @@ def lib():
         L.rsd_cross_bilateral_blur.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp]
         L.rsd_temporal_ao.restype = st
         L.rsd_temporal_ao.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, C.POINTER(Camera), vp, vp, vp, vp]
+        L.rsd_temporal_depth_peel.restype = st
+        L.rsd_temporal_depth_peel.argtypes = [vp, vp, u32, u32, C.POINTER(Camera), vp, vp, f32, C.c_int32, vp, vp]
         L.rsd_ao_flicker_mask.restype = st
         L.rsd_ao_flicker_mask.argtypes = [vp, vp, u32, u32, C.POINTER(Camera), vp, vp]
         L.rsd_binary_dilation.restype = st

@@ -5,7 +5,11 @@ chain (scripts/SVAO.py: SVAO -> CrossBilateralBlur -> TemporalAO -> Switch -> Im
 TemporalAO mirrors Source/RenderPasses/TemporalAO/TemporalAO.cpp: properties `enabled` and
 `useStableMask` (:42-43), previous-frame depth / AO / history textures (re)allocated on the first
 enabled frame and reset when disabled (:128-140), prevViewToCurView = viewMat * inverse(prevViewMat)
-(:156), and the end-of-frame copies into the history textures (:165-168)."""
+(:156), and the end-of-frame copies into the history textures (:165-168).
+
+TemporalDepthPeel (rsd_temporal_depth_peel) is the temporal producer of DualDepth SVAO's second depth layer
+(scripts/SVAO_depth.py: LinearizeDepth -> TemporalDepthPeel -> DepthSelect -> SVAO.depth2); it mirrors
+Source/RenderPasses/TemporalDepthPeel/TemporalDepthPeel.cpp's Iterative implementation."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,6 +38,12 @@ def prev_view_to_cur_view(cam: abi.Camera, prev_cam: abi.Camera) -> np.ndarray:
     inv[:3, :3] = p[:3, :3].T
     inv[:3, 3] = -p[:3, :3].T @ p[:3, 3]
     return (view_matrix(cam) @ inv).astype(np.float32)
+
+
+def cur_view_to_prev_view(cam: abi.Camera, prev_cam: abi.Camera) -> np.ndarray:
+    """prevViewMat * inverse(viewMat) (TemporalDepthPeel.cpp:193), row-major float32: the inverse
+    transform of prev_view_to_cur_view, built the same way (float64, rounded once)."""
+    return prev_view_to_cur_view(prev_cam, cam)
 
 
 def motion_vectors(cam: abi.Camera, prev_cam: abi.Camera, linear_z, out=None, stream=None):
@@ -99,6 +109,47 @@ class TemporalAO:
         self.prev_ao.copy_(ao_out)
         self.prev_history.copy_(self.history)
         return ao_out
+
+
+class TemporalDepthPeel:
+    """One TemporalDepthPeel pass instance (TemporalDepthPeel.cpp, Implementation::Iterative): the second
+    depth layer of DualDepth SVAO found by marching each pixel's view ray through the previous frame's
+    second layer (rsd_temporal_depth_peel); keeps that previous layer.  `min_separation` is the pass's
+    minSeparationDistance, `iterations` its mIterations."""
+
+    def __init__(self, min_separation: float = 0.5, iterations: int = 32):
+        self.min_separation = min_separation
+        self.iterations = iterations
+        self.prev_depth2 = None
+
+    def reset(self):
+        """TemporalDepthPeel::compile (:148-152): the next frame starts from an empty history."""
+        self.prev_depth2 = None
+
+    def execute(self, linear_z, cam: abi.Camera, prev_cam: abi.Camera, depth2_out=None):
+        """linear_z: (H, W) float32.  Returns depth2_out (allocated when None): the reprojected second
+        layer where the search finds one behind linear_z + min_separation, linear_z elsewhere (and on
+        the first frame, whose history is all zeros)."""
+        import torch
+        H, W = linear_z.shape
+        if depth2_out is None:
+            depth2_out = torch.empty_like(linear_z)
+        for t in (linear_z, depth2_out):
+            if t.dtype != torch.float32 or tuple(t.shape) != (H, W) or not t.is_contiguous() or \
+                    t.device != linear_z.device:
+                raise ValueError(f"TemporalDepthPeel: expected a contiguous float32 {(H, W)} tensor, "
+                                 f"got {t.dtype} {tuple(t.shape)}")
+        if self.prev_depth2 is None or tuple(self.prev_depth2.shape) != (H, W):  # allocatePrevFrameTexture
+            self.prev_depth2 = torch.zeros_like(linear_z)
+        c2p = np.ascontiguousarray(cur_view_to_prev_view(cam, prev_cam), np.float32)
+        p2c = np.ascontiguousarray(prev_view_to_cur_view(cam, prev_cam), np.float32)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        abi.check(abi.lib().rsd_temporal_depth_peel(_ptr(linear_z), _ptr(self.prev_depth2), W, H, C.byref(cam),
+                                                    c2p.ctypes.data_as(C.c_void_p), p2c.ctypes.data_as(C.c_void_p),
+                                                    float(self.min_separation), int(self.iterations),
+                                                    _ptr(depth2_out), s), "rsd_temporal_depth_peel")
+        self.prev_depth2.copy_(depth2_out)  # :264 save this frame's layer for the next
+        return depth2_out
 
 
 class TAA:
