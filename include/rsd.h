@@ -364,6 +364,33 @@ rsd_status rsd_rtao(rsd_scene* scene, const rsd_rtao_params* params, uint32_t wi
 rsd_status rsd_rtao_pack(const float* d_ambient, const float* d_ray_distance, uint32_t count, uint8_t* d_ambient_unorm8,
                          uint16_t* d_ray_distance_f16, rsd_stream stream);
 
+/* --- HBAO: horizon-based AO with interleaved texture access (RenderPasses/HBAO; the screen-space baseline) ---
+ * HBAO.ps.slang:134-247 over the 16 quarter-size layers of a deinterleaved linear depth (rsd_deinterleave,
+ * rsd_graph.h): layer s = 4 dy + dx shades the pixels (4 x + dx, 4 y + dy) with rand[s], 8 directions x 4
+ * steps of point taps (clamp addressing) into its own layer, and writes (bright, dark) -- the dark channel has
+ * no distance falloff -- into layer s of d_ambient_layers; rsd_interleave gives the frame.  DualDepth reads
+ * d_depth2_layers for the taps in the positive hemisphere but beyond the radius and keeps the per-channel
+ * max.  Texels outside the scissor guard_band / 4 (HBAO.cpp:181) are not written; a layer texel whose
+ * full-resolution pixel lies outside the frame (sizes that are no multiple of 4) is written like any other.
+ * Exact numerics only (DESIGN.md section 2 "HBAO"). */
+typedef struct {
+    float radius;          /* view-space radius, > 0 [1] */
+    float ndotv_bias;      /* the pass's depthBias property [0.1] */
+    float power_exponent;  /* [2] */
+    uint32_t depth_mode;   /* 0 SingleDepth, 1 DualDepth; 2 (StochasticDepth) is refused: RSD_ERR_UNSUPPORTED */
+    uint32_t guard_band;   /* full-resolution pixels; the scissor on the layers is guard_band / 4 */
+    float rand[16][4];     /* per layer (sin theta, cos theta, r1, r2); rsd_hbao_noise_table has the pass's */
+} rsd_hbao_params;
+/* HBAO::genNoiseTexture (HBAO.cpp:225-251): 16 entries from MT19937(0), one generator for all; per entry theta
+ * in [0, 2 * 3.141f), r1, r2, each draw u mapped to (float)u / 2^32 (host only) */
+rsd_status rsd_hbao_noise_table(float out[16][4]);
+/* d_depth_layers / d_depth2_layers: 16 layers of qw x qh R32F, qw = ceil(width / 4), qh = ceil(height / 4)
+ * (d_depth2_layers may be NULL unless depth_mode is DualDepth).  d_normal_w: RGBA32F, width x height
+ * (GBufferRaster.faceNormalW).  d_ambient_layers: 16 layers of qw x qh RG8Unorm. */
+rsd_status rsd_hbao(const float* d_depth_layers, const float* d_depth2_layers, const float* d_normal_w,
+                    uint32_t width, uint32_t height, const rsd_camera* cam, const rsd_hbao_params* params,
+                    uint8_t* d_ambient_layers, rsd_stream stream);
+
 /* DepthPeeling (DepthPeeling.3d.slang:16-28, DepthPeeling.cpp:91-115): the next depth layer behind
  * d_prev_linear_z (linear view depth, width x height R32F), the producer of DualDepth's d_depth2.
  * Per pixel the primary ray, culling and alpha test of rsd_gbuffer_raster; a hit of linear depth z is

@@ -81,6 +81,14 @@ rsd_status rsd_cross_bilateral_blur(const uint8_t* d_src, const float* d_linear_
                                     uint8_t* d_pingpong, uint8_t* d_dst, uint32_t width, uint32_t height,
                                     uint32_t guard_band, uint32_t kernel_radius, uint32_t better_slope,
                                     rsd_stream stream);
+/* The same for a source of src_texel_bytes-byte texels, 1 (R8Unorm) or 2 (RG8Unorm: scripts/HBAO.py blurs the
+ * interleaved (bright, dark) map): the x pass reads byte 0 of each source texel, the shader's `.x`
+ * (CrossBilateralBlur.ps.slang:72); d_pingpong and d_dst stay R8Unorm.  rsd_cross_bilateral_blur is this
+ * with src_texel_bytes = 1. */
+rsd_status rsd_cross_bilateral_blur_src(const uint8_t* d_src, uint32_t src_texel_bytes, const float* d_linear_z,
+                                        uint32_t z_w, uint32_t z_h, uint8_t* d_pingpong, uint8_t* d_dst,
+                                        uint32_t width, uint32_t height, uint32_t guard_band, uint32_t kernel_radius,
+                                        uint32_t better_slope, rsd_stream stream);
 /* RayMinMaxLength (RayMinMaxLength.ps.slang:4-16): the SD ray interval length per texel,
  * max(0, asfloat(rayMax) - asfloat(rayMin)) / 32, and 0 where rayMax is 0 (R32Float). */
 rsd_status rsd_ray_min_max_length(const uint32_t* d_ray_min, const uint32_t* d_ray_max, uint32_t width,

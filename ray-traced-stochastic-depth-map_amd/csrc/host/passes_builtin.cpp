@@ -13,7 +13,9 @@
 //   SVAO                  SVAO.cpp                   rsd_svao_* + a nested "Stochastic Depth"
 //                                                    graph holding StochasticDepthMapRT
 //
-//   CrossBilateralBlur    CrossBilateralBlur.cpp     rsd_cross_bilateral_blur
+//   HBAO                  HBAO.cpp                   rsd_hbao (16 deinterleaved layers in and out)
+//
+//   CrossBilateralBlur    CrossBilateralBlur.cpp     rsd_cross_bilateral_blur_src (R8Unorm or RG8Unorm in)
 //   ImageEquation         ImageEquation.cpp          rsd_image_equation_compile / _run
 //   Switch                Switch.cpp                 copy of the selected input
 //   TemporalAO            TemporalAO.cpp             rsd_temporal_ao (enabled = False: copy)
@@ -377,6 +379,84 @@ private:
     float *ambient_ = nullptr, *distance_ = nullptr;  // rsd_rtao's float32 results, converted into the outputs
 };
 
+// ------------------------------------------------------------------------------ HBAO
+// HBAO.cpp:64-76 Properties (radius, depthMode, depthBias, exponent), :104-125 reflect, :140-194 execute;
+// HBAO.ps.slang.  depth / depth2: the 16 layers DeinterleaveTexture makes of a linear depth; ambientMap: 16
+// RG8Unorm layers (bright, dark) for InterleaveTexture.  The Rand table is the pass's own (genNoiseTexture,
+// rsd_hbao_noise_table).  mEnabled is a GUI member in the reference; librsd accepts it as the optional
+// property `enabled` (false: ambientMap cleared to 1).  depth2 is required in the reference's reflection; here
+// only DualDepth, the one mode that reads it, requires it.
+class HBAOPass : public RenderPass {
+public:
+    explicit HBAOPass(const Properties& p) {
+        props_ = p;
+        prm_.radius = (float)p.getFloat("radius", 1.0);            // HBAOData.slang:38
+        prm_.ndotv_bias = (float)p.getFloat("depthBias", 0.1);     // :40
+        prm_.power_exponent = (float)p.getFloat("exponent", 2.0);  // :41
+        prm_.depth_mode = enumProp(p, "depthMode", kDepthModeNames, 0);  // HBAO.h:67
+        enabled_ = p.getBool("enabled", true);
+        if (!(prm_.radius > 0.0f)) throw std::runtime_error("HBAO: radius must be positive");
+        check(rsd_hbao_noise_table(prm_.rand), "HBAO");
+    }
+    Reflection reflect(const CompileData& cd) override {
+        if (prm_.depth_mode > 1)  // the shader's third mode reads a texture HBAO.cpp never binds (:119, :177)
+            throw Unsupported("HBAO: depthMode must be SingleDepth or DualDepth");
+        Reflection r;
+        Field& d = r.addInput("depth", "linear-depth (deinterleaved version)");
+        d.format = Format::R32Float;
+        d.layers = 16;
+        Field& d2 = r.addInput("depth2", "linear-depth2 (deinterleaved version)");
+        d2.format = Format::R32Float;
+        d2.layers = 16;
+        d2.optional = prm_.depth_mode != 1;
+        r.addInput("normals", "normals").format = Format::RGBA32Float;
+        Field& o = r.addOutput("ambientMap", "ambient occlusion (deinterleaved)");
+        o.format = Format::RG8Unorm;
+        o.width = (cd.defaultWidth + 3) / 4;  // :107-111
+        o.height = (cd.defaultHeight + 3) / 4;
+        o.layers = 16;
+        return r;
+    }
+    void setScene(Context&, const SceneRef* s) override { scene_ = s; }
+    void execute(Context& ctx, const RenderData& rd) override {
+        if (!scene_) return;  // :142
+        Texture* depth = rd["depth"];
+        Texture* depth2 = rd["depth2"];
+        Texture* normals = rd["normals"];
+        Texture* out = rd["ambientMap"];
+        if (!enabled_) {  // :150-155
+            if (hipMemsetAsync(out->ptr, 0xff, out->bytes(), ctx.stream) != hipSuccess)
+                throw std::runtime_error("HBAO: clear failed");
+            return;
+        }
+        const uint32_t W = rd.defaultWidth(), H = rd.defaultHeight(), qw = (W + 3) / 4, qh = (H + 3) / 4;
+        auto layers16 = [&](const Texture* t, Format f) {
+            return t->format == f && t->layers == 16 && t->width == qw && t->height == qh;
+        };
+        if (!layers16(out, Format::RG8Unorm))
+            throw std::runtime_error("HBAO: ambientMap must be 16 RG8Unorm layers of ceil(w/4) x ceil(h/4)");
+        if (!layers16(depth, Format::R32Float))
+            throw Unsupported("HBAO: depth must be 16 R32Float layers of ceil(w/4) x ceil(h/4) (DeinterleaveTexture)");
+        if (prm_.depth_mode == 1 && (!depth2 || !layers16(depth2, Format::R32Float)))
+            throw Unsupported("HBAO: depthMode DualDepth needs 'depth2', 16 R32Float layers like 'depth'");
+        if (normals->format != Format::RGBA32Float || normals->layers != 1 || normals->width != W || normals->height != H)
+            throw Unsupported("HBAO: normals must be RGBA32Float at the frame size");
+        auto& dict = rd.getDictionary();  // :179-181
+        auto it = dict.find("guardBand");
+        const int64_t g = it != dict.end() && std::holds_alternative<int64_t>(it->second)
+                              ? std::get<int64_t>(it->second) : 0;
+        prm_.guard_band = (uint32_t)(g > 0 ? g : 0);
+        check(rsd_hbao((const float*)depth->ptr, prm_.depth_mode == 1 ? (const float*)depth2->ptr : nullptr,
+                       (const float*)normals->ptr, W, H, &scene_->camera, &prm_, (uint8_t*)out->ptr, ctx.stream),
+              "HBAO");
+    }
+
+private:
+    const SceneRef* scene_ = nullptr;
+    bool enabled_;
+    rsd_hbao_params prm_{};
+};
+
 // ------------------------------------------------------------------------------ StochasticDepthMapRT
 // StochasticDepthMapRT.cpp:135-155 Properties, :190-216 reflect, :231-331 execute.
 class StochasticDepthMapRTPass : public RenderPass {
@@ -671,6 +751,7 @@ public:
     ~CrossBilateralBlurPass() override { (void)hipFree(pingpong_); }
     Reflection reflect(const CompileData&) override {
         Reflection r;
+        // the format a stub producer gets; execute accepts the connected R8Unorm or RG8Unorm
         r.addInput("color", "color image to be blurred").format = Format::R8Unorm;
         r.addInput("linear depth", "linear depth").format = Format::R32Float;
         r.addOutput("colorOut", "blurred color").format = Format::R8Unorm;
@@ -686,9 +767,14 @@ public:
         Texture* in = rd["color"];
         Texture* z = rd["linear depth"];
         Texture* out = rd["colorOut"];
-        if (in->format != Format::R8Unorm || in->width != out->width || in->height != out->height)
-            throw Unsupported("CrossBilateralBlur: the color input must be R8Unorm at the output size");
+        // the shader reads `.x` of the source (CrossBilateralBlur.ps.slang:72): scripts/HBAO.py feeds the
+        // interleaved RG8Unorm (bright, dark) map; colorOut stays R8Unorm (CrossBilateralBlur.h:67)
+        if ((in->format != Format::R8Unorm && in->format != Format::RG8Unorm) || in->width != out->width ||
+            in->height != out->height)
+            throw Unsupported("CrossBilateralBlur: the color input must be R8Unorm or RG8Unorm at the output size");
         if (!enabled_) {  // :120-124 blit
+            if (in->format != Format::R8Unorm)
+                throw Unsupported("CrossBilateralBlur: enabled = False copies the input, which must be R8Unorm");
             if (hipMemcpyAsync(out->ptr, in->ptr, out->bytes(), hipMemcpyDeviceToDevice, ctx.stream) != hipSuccess)
                 throw std::runtime_error("CrossBilateralBlur: copy failed");
             return;
@@ -699,9 +785,10 @@ public:
         const int64_t g = it != dict.end() && std::holds_alternative<int64_t>(it->second)
                               ? std::get<int64_t>(it->second) : 0;
         for (uint32_t k = 0; k < repetitions_; ++k)  // :136-148: every repetition blurs the input again
-            check(rsd_cross_bilateral_blur((const uint8_t*)in->ptr, (const float*)z->ptr, z->width, z->height,
-                                           (uint8_t*)pingpong_, (uint8_t*)out->ptr, out->width, out->height,
-                                           (uint32_t)g, radius_, betterSlope_ ? 1u : 0u, ctx.stream),
+            check(rsd_cross_bilateral_blur_src((const uint8_t*)in->ptr, (uint32_t)formatBytes(in->format),
+                                               (const float*)z->ptr, z->width, z->height, (uint8_t*)pingpong_,
+                                               (uint8_t*)out->ptr, out->width, out->height, (uint32_t)g, radius_,
+                                               betterSlope_ ? 1u : 0u, ctx.stream),
                   "CrossBilateralBlur");
     }
 
@@ -1175,6 +1262,7 @@ void registerBuiltinPasses(PluginRegistry& r) {
     r.registerClass("CompressNormals", "view-space 2x8 octahedral normals", factory<CompressNormalsPass>());
     r.registerClass("DepthPeeling", "next depth layer behind a linear depth map", factory<DepthPeelingPass>());
     r.registerClass("RTAO", "ray-traced ambient occlusion (ground truth)", factory<RTAOPass>());
+    r.registerClass("HBAO", "horizon-based AO over 16 deinterleaved quarter-size layers", factory<HBAOPass>());
     r.registerClass("StochasticDepthMapRT", "ray-traced stochastic depth map", factory<StochasticDepthMapRTPass>());
     r.registerClass("SVAO", "stochastic-depth volumetric ambient occlusion", factory<SVAOPass>());
     r.registerClass("CrossBilateralBlur", "depth-aware cross bilateral blur", factory<CrossBilateralBlurPass>());

@@ -35,6 +35,7 @@ struct BlurArgs {
     const float* z;
     uint8_t* dst;
     int W, H, g;
+    int srcTexel;  // bytes per source texel; the blur reads byte 0 (CrossBilateralBlur.ps.slang:72 `.x`)
     float dirX, dirY;
     float uvMinX, uvMinY, uvMaxX, uvMaxY;
     int zW, zH;
@@ -59,7 +60,7 @@ __global__ void __launch_bounds__(kPostW * kPostH) blur_kernel(BlurArgs a) {
         const float u = fminf(fmaxf(tcx + (float)d * dux, a.uvMinX), a.uvMaxX);
         const float v = fminf(fmaxf(tcy + (float)d * duy, a.uvMinY), a.uvMaxY);
         dc[R + d] = a.z[(size_t)point_texel(v, a.zH) * a.zW + point_texel(u, a.zW)];
-        ac[R + d] = unorm8_to_float(a.src[(size_t)point_texel(v, a.H) * a.W + point_texel(u, a.W)]);
+        ac[R + d] = unorm8_to_float(a.src[((size_t)point_texel(v, a.H) * a.W + point_texel(u, a.W)) * a.srcTexel]);
     }
     const float sigma = ((float)R + 1.0f) * 0.5f;
     const float falloff = 1.0f / (2.0f * sigma * sigma);
@@ -624,10 +625,15 @@ __global__ void __launch_bounds__(kPostW * kPostH) image_equation_kernel(EqArgs 
 
 using namespace rsd;
 
-extern "C" rsd_status rsd_cross_bilateral_blur(const uint8_t* d_src, const float* d_linear_z, uint32_t z_w,
-                                               uint32_t z_h, uint8_t* d_pingpong, uint8_t* d_dst, uint32_t width,
-                                               uint32_t height, uint32_t guard_band, uint32_t kernel_radius,
-                                               uint32_t better_slope, rsd_stream stream) {
+extern "C" rsd_status rsd_cross_bilateral_blur_src(const uint8_t* d_src, uint32_t src_texel_bytes,
+                                                   const float* d_linear_z, uint32_t z_w, uint32_t z_h,
+                                                   uint8_t* d_pingpong, uint8_t* d_dst, uint32_t width,
+                                                   uint32_t height, uint32_t guard_band, uint32_t kernel_radius,
+                                                   uint32_t better_slope, rsd_stream stream) {
+    if (src_texel_bytes != 1 && src_texel_bytes != 2) {
+        set_error("rsd_cross_bilateral_blur_src: src_texel_bytes must be 1 (R8Unorm) or 2 (RG8Unorm)");
+        return RSD_ERR_INVALID_ARG;
+    }
     if (!d_src || !d_linear_z || !d_pingpong || !d_dst || width == 0 || height == 0 || z_w == 0 || z_h == 0 ||
         kernel_radius < 1 || kernel_radius > 20 || 2 * guard_band >= width || 2 * guard_band >= height) {
         set_error("rsd_cross_bilateral_blur: invalid argument (radius 1..20, guard band inside the frame)");
@@ -649,6 +655,7 @@ extern "C" rsd_status rsd_cross_bilateral_blur(const uint8_t* d_src, const float
     hipStream_t s = (hipStream_t)stream;
     for (int pass = 0; pass < 2; ++pass) {  // blur in x into the ping-pong image, then in y
         a.src = pass == 0 ? d_src : d_pingpong;
+        a.srcTexel = pass == 0 ? (int)src_texel_bytes : 1;  // the ping-pong image and the output stay R8Unorm
         a.dst = pass == 0 ? d_pingpong : d_dst;
         a.dirX = pass == 0 ? 1.0f : 0.0f;
         a.dirY = pass == 0 ? 0.0f : 1.0f;
@@ -662,6 +669,14 @@ extern "C" rsd_status rsd_cross_bilateral_blur(const uint8_t* d_src, const float
         if (e != hipSuccess) return hip_fail(e, "blur_kernel launch");
     }
     return RSD_OK;
+}
+
+extern "C" rsd_status rsd_cross_bilateral_blur(const uint8_t* d_src, const float* d_linear_z, uint32_t z_w,
+                                               uint32_t z_h, uint8_t* d_pingpong, uint8_t* d_dst, uint32_t width,
+                                               uint32_t height, uint32_t guard_band, uint32_t kernel_radius,
+                                               uint32_t better_slope, rsd_stream stream) {
+    return rsd_cross_bilateral_blur_src(d_src, 1u, d_linear_z, z_w, z_h, d_pingpong, d_dst, width, height, guard_band,
+                                        kernel_radius, better_slope, stream);
 }
 
 namespace {

@@ -112,6 +112,20 @@ class RTAOParams(C.Structure):  # rsd_rtao_params; the defaults of RTAO.h / RTAO
 RTAO_SAMPLE_COUNT = 5312  # rsd.h RSD_RTAO_SAMPLE_COUNT
 
 
+class HBAOParams(C.Structure):  # rsd_hbao_params; the defaults of HBAOData.slang
+    _fields_ = [("radius", C.c_float), ("ndotv_bias", C.c_float), ("power_exponent", C.c_float),
+                ("depth_mode", C.c_uint32), ("guard_band", C.c_uint32), ("rand", (C.c_float * 4) * 16)]
+
+    def __init__(self, radius=1.0, ndotv_bias=0.1, power_exponent=2.0, depth_mode=0, guard_band=0, rand=None):
+        """rand: None for the pass's own table (rsd_hbao_noise_table), or 16 x 4 floats (sin, cos, r1, r2)."""
+        super().__init__(radius, ndotv_bias, power_exponent, int(depth_mode), int(guard_band))
+        if rand is None:
+            check(lib().rsd_hbao_noise_table(self.rand), "rsd_hbao_noise_table")
+        else:
+            for i, row in enumerate(rand):
+                self.rand[i][:] = [float(v) for v in row]
+
+
 class HaloRegion(C.Structure):  # rsd_halo_region
     _fields_ = [("row0", C.c_uint32), ("row1", C.c_uint32), ("out", C.c_void_p), ("stride", C.c_uint32),
                 ("period", C.c_uint32), ("count", C.c_void_p)]
@@ -199,7 +213,8 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_comm_local_create", "rsd_comm_null_create", "rsd_comm_release", "rsd_comm_info", "rsd_comm_all_gather", "rsd_comm_exchange",
            "rsd_band_frame_create", "rsd_band_frame_front", "rsd_band_frame_back", "rsd_band_frame_stats",
            "rsd_band_frame_release", "rsd_band_frame_set_split", "rsd_depth_peel", "rsd_gbuffer_world",
-           "rsd_rtao", "rsd_rtao_sample_table", "rsd_rtao_ray_t_max", "rsd_rtao_pack"]
+           "rsd_rtao", "rsd_rtao_sample_table", "rsd_rtao_ray_t_max", "rsd_rtao_pack", "rsd_hbao",
+           "rsd_hbao_noise_table"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -213,7 +228,8 @@ GRAPH_EXPORTS = ["rsd_graph_create", "rsd_graph_destroy", "rsd_graph_create_pass
                  "rsd_cross_bilateral_blur", "rsd_image_equation_compile", "rsd_image_equation_info",
                  "rsd_image_equation_run", "rsd_image_equation_release", "rsd_temporal_ao",
                  "rsd_motion_vectors", "rsd_motion_vectors_raster", "rsd_taa", "rsd_ao_flicker_mask", "rsd_binary_dilation",
-                 "rsd_deinterleave", "rsd_interleave", "rsd_ray_min_max_length", "rsd_temporal_depth_peel"]
+                 "rsd_deinterleave", "rsd_interleave", "rsd_ray_min_max_length", "rsd_temporal_depth_peel",
+                 "rsd_cross_bilateral_blur_src"]
 
 FMT_R32F, FMT_RG32F, FMT_RGBA32F, FMT_R16U, FMT_R8U, FMT_R8UNORM, FMT_R32U, FMT_UNKNOWN = range(8)
 FMT_R16F, FMT_RG16F, FMT_RGBA16F, FMT_RG8UNORM = 8, 9, 10, 11
@@ -358,6 +374,10 @@ def lib():
         L.rsd_rtao_ray_t_max.argtypes = [C.POINTER(RTAOParams), C.POINTER(f32)]
         L.rsd_rtao_pack.restype = st
         L.rsd_rtao_pack.argtypes = [vp, vp, u32, vp, vp, vp]
+        L.rsd_hbao.restype = st
+        L.rsd_hbao.argtypes = [vp, vp, vp, u32, u32, C.POINTER(Camera), C.POINTER(HBAOParams), vp, vp]
+        L.rsd_hbao_noise_table.restype = st
+        L.rsd_hbao_noise_table.argtypes = [vp]
         L.rsd_depth_peel.restype = st
         L.rsd_depth_peel.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, f32, u32, vp, vp]
         L.rsd_linearize_depth.restype = st
@@ -390,6 +410,8 @@ def lib():
             fn.argtypes = args
         L.rsd_cross_bilateral_blur.restype = st
         L.rsd_cross_bilateral_blur.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp]
+        L.rsd_cross_bilateral_blur_src.restype = st
+        L.rsd_cross_bilateral_blur_src.argtypes = [vp, u32, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp]
         L.rsd_temporal_ao.restype = st
         L.rsd_temporal_ao.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, C.POINTER(Camera), vp, vp, vp, vp]
         L.rsd_temporal_depth_peel.restype = st

@@ -398,6 +398,41 @@ class Renderer:
                                      _ptr(ambient), _ptr(ray_distance), None, self.stream), "rsd_rtao")
         return ambient, ray_distance
 
+    def hbao(self, depth_mode: int = abi.DEPTH_SINGLE, depth2=None, **params):
+        """Horizon-based AO of this renderer's frame (rsd_hbao, the reference's HBAO pass with its
+        DeinterleaveTexture / InterleaveTexture neighbours): self.depth is deinterleaved into 16 quarter-size
+        layers, shaded with the world-space face normals, which rsd_gbuffer_raster renders here with the
+        config's cull mode (kept as self.face_normal_w), and interleaved back.  Call it after gbuffer().
+        depth_mode DEPTH_DUAL reads a second linear depth layer: depth2, or self.depth2 (depth_peel()).
+        params: abi.HBAOParams members (radius, ndotv_bias, power_exponent, guard_band -- default the
+        config's --, rand).  Returns the (bright, dark) map, a uint8 tensor of the frame size x 2."""
+        t, L, W, H = self.torch, abi.lib(), self.cfg.fb_w, self.cfg.fb_h
+        params.setdefault("guard_band", self.cfg.guard_band)
+        prm = abi.HBAOParams(depth_mode=depth_mode, **params)
+        if depth_mode == abi.DEPTH_DUAL:
+            depth2 = self.depth2 if depth2 is None else depth2
+            if depth2 is None or tuple(depth2.shape) != (H, W) or depth2.dtype != t.float32:
+                raise ValueError("hbao(depth_mode=DEPTH_DUAL) needs depth2, a float32 tensor of the frame size")
+        dv, qw, qh = self.depth.device, (W + 3) // 4, (H + 3) // 4
+        raster_depth = t.empty((H, W), dtype=t.float32, device=dv)
+        self.face_normal_w = t.empty((H, W, 4), dtype=t.float32, device=dv)
+        abi.check(L.rsd_gbuffer_raster(self.gscene.h, C.byref(self.cam), W, H, self.cfg.cull_mode, _ptr(raster_depth),
+                                       _ptr(self.face_normal_w), self.stream), "rsd_gbuffer_raster")
+        layers = t.empty((16, qh, qw), dtype=t.float32, device=dv)
+        abi.check(L.rsd_deinterleave(_ptr(self.depth), W, H, 4, _ptr(layers), self.stream), "rsd_deinterleave")
+        layers2 = None
+        if depth_mode == abi.DEPTH_DUAL:
+            layers2 = t.empty_like(layers)
+            abi.check(L.rsd_deinterleave(_ptr(depth2.contiguous()), W, H, 4, _ptr(layers2), self.stream),
+                      "rsd_deinterleave")
+        # texels outside the guard-band scissor are not written: they read 1 (the cleared value)
+        ambient_layers = t.full((16, qh, qw, 2), 255, dtype=t.uint8, device=dv)
+        abi.check(L.rsd_hbao(_ptr(layers), _ptr(layers2), _ptr(self.face_normal_w), W, H, C.byref(self.cam),
+                             C.byref(prm), _ptr(ambient_layers), self.stream), "rsd_hbao")
+        ambient = t.empty((H, W, 2), dtype=t.uint8, device=dv)
+        abi.check(L.rsd_interleave(_ptr(ambient_layers), W, H, 2, _ptr(ambient), self.stream), "rsd_interleave")
+        return ambient
+
     def clear_intervals(self):
         abi.check(abi.lib().rsd_svao_clear_intervals(_ptr(self.ray_min), _ptr(self.ray_max), self.sd_w * self.sd_h,
                                                      self.stream), "rsd_svao_clear_intervals")
