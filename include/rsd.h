@@ -418,6 +418,37 @@ rsd_status rsd_sd_trace(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_pa
                         float* d_sd_out, uint32_t sd_w, uint32_t sd_h,
                         rsd_counters* counters, rsd_stream stream);
 
+/* StochasticDepthMap (StochasticDepth.ps.slang:57-126, Stencil.ps.slang, StochasticDepthMap.cpp:189-327): the
+ * raster producer of the stochastic depth map, the one Ray-SD is compared with.  Per SD texel the pixel-centre
+ * primary ray of rsd_gbuffer_raster over an sd_w x sd_h image; every triangle it crosses inside [near, far] is a
+ * fragment.  A fragment is discarded by the alpha test (LOD 0), when its non-linear depth is <= the first layer
+ * d_depth sampled at the texel centre (point sampling for an odd divisor (int)(depth_w / (float)sd_w + .5f),
+ * bilinear for an even one, wrap addressing), and -- ray_interval with both maps given -- when its distance to
+ * the camera is <= asfloat(rayMin) or >= asfloat(rayMax) (a zero word: no bound).  A surviving fragment covers
+ * floor(alpha N + hash(world position)) of the N samples, chosen by the stratified table (none: discarded),
+ * and every covered sample keeps the minimum of its values: (z - near) / (far - near) of the linear depth z with
+ * linearize, else the non-linear depth.  Samples no fragment covers hold 1.0.  use_stencil (the reference's
+ * depth formats with stencil): texels whose d_stencil_mask byte -- without a mask: whose d_ray_max word -- is 0
+ * receive no fragment.  d_ray_min, d_ray_max and d_stencil_mask may be NULL.  d_sd_out has rsd_sd_trace's
+ * layout, [layer][y][x][min(N,4)] R32F.  The result is independent of the fragment order: one correct bit
+ * pattern.  implementation: Default and CoverageMask are this path; ReservoirSampling (order-dependent) and
+ * KBuffer are RSD_ERR_UNSUPPORTED.  sample_count: 1, 2, 4, 8 or 16.  Stream-ordered; the first call for a
+ * (device, N) uploads the stratified table it shares with rsd_sd_trace. */
+typedef struct {
+    uint32_t sample_count;   /* SampleCount N [8] */
+    float alpha;             /* Alpha [0.2] */
+    uint32_t cull_mode;      /* CullMode: rsd_cull_mode [Back] */
+    uint32_t linearize;      /* linearize [1] */
+    uint32_t alpha_test;     /* AlphaTest [1]; no-op on a scene without alpha materials */
+    uint32_t implementation; /* Implementation: rsd_sd_impl [Default] */
+    uint32_t ray_interval;   /* RayInterval [1] */
+    uint32_t use_stencil;    /* depthFormat has stencil (D32FloatS8X24, D24UnormS8) [0: D32Float] */
+} rsd_sd_raster_params;
+rsd_status rsd_sd_raster(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_raster_params* params,
+                         const float* d_depth, uint32_t depth_w, uint32_t depth_h,
+                         const uint32_t* d_ray_min, const uint32_t* d_ray_max, const uint8_t* d_stencil_mask,
+                         float* d_sd_out, uint32_t sd_w, uint32_t sd_h, rsd_stream stream);
+
 /* SVAO.cpp:330-341: rayMax <- 0, rayMin <- asuint(FLT_MAX) */
 /* Words of rsd_sd_params.d_tile_state for an sd_w x sd_h map: three per 8x8 tile (a stamp; since ABI v8 a texel mask). */
 uint32_t rsd_sd_tile_state_count(uint32_t sd_w, uint32_t sd_h);

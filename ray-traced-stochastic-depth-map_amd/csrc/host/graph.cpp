@@ -286,7 +286,16 @@ void RenderGraph::compile(Context& ctx, uint32_t width, uint32_t height, bool al
     width_ = width;
     height_ = height;
     CompileData cd{width, height};
-    for (auto& [n, node] : passes_) node.refl = node.pass->reflect(cd);
+    for (auto& [n, node] : passes_) {
+        std::set<std::string> connected;
+        for (auto& e : edges_)
+            if (e.dstPass == n && !e.dstField.empty()) connected.insert(e.dstField);
+        for (auto& [key, tex] : inputs_)
+            if (tex && splitName(key).first == n) connected.insert(splitName(key).second);
+        CompileData own = cd;
+        own.connected = &connected;
+        node.refl = node.pass->reflect(own);
+    }
 
     // RenderGraphCompiler.cpp:121-172: keep the passes that feed a marked output
     std::set<std::string> need;

@@ -21,6 +21,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <variant>
@@ -93,6 +94,9 @@ struct Reflection {
 
 struct CompileData {
     uint32_t defaultWidth = 0, defaultHeight = 0;
+    // the pass's input fields that an edge or an external texture feeds (Falcor's
+    // CompileData::connectedResources); null: not known
+    const std::set<std::string>* connected = nullptr;
 };
 
 // The frame's scene: the uploaded BVH and the camera (Falcor Scene + Camera subset).

@@ -10,7 +10,8 @@
 //   DepthPeeling          DepthPeeling.cpp:54-115    rsd_depth_peel (DualDepth's second layer)
 //   RTAO                  RTAO.cpp:51-158            rsd_rtao (ray-traced AO, the ground truth)
 //   StochasticDepthMapRT  StochasticDepthMapRT.cpp   rsd_sd_trace            (the hot path)
-//   SVAO                  SVAO.cpp                   rsd_svao_* + a nested "Stochastic Depth"
+//   StochasticDepthMap    StochasticDepthMap.cpp     rsd_sd_raster           (the raster producer)
+//   SVAO                  SVAO.cpp                  rsd_svao_* + a nested "Stochastic Depth"
 //                                                    graph holding StochasticDepthMapRT
 //
 //   HBAO                  HBAO.cpp                   rsd_hbao (16 deinterleaved layers in and out)
@@ -526,11 +527,84 @@ private:
     rsd_sd_params prm_{};
 };
 
+// ------------------------------------------------------------------------------ StochasticDepthMap
+// The raster producer of the stochastic depth map (rsd_sd_raster): StochasticDepthMap.cpp:158-174 Properties
+// with the defaults of StochasticDepthMap.h, :189-200 reflect, :222-327 execute.  The map is stored like the
+// RT pass's, [layer][y][x][min(N,4)] R32F, whatever depthFormat says; the format only decides whether the
+// stencil exists (:232-236).  The unorm formats would quantise the stored depths and are refused.
+class StochasticDepthMapPass : public RenderPass {
+public:
+    explicit StochasticDepthMapPass(const Properties& p) {
+        props_ = p;
+        prm_.sample_count = (uint32_t)p.getInt("SampleCount", 8);
+        prm_.alpha = (float)p.getFloat("Alpha", 0.2);
+        prm_.cull_mode = toRsdCull(enumProp(p, "CullMode", kCullNames, 2));
+        prm_.linearize = p.getBool("linearize", true);
+        prm_.alpha_test = p.getBool("AlphaTest", true);
+        prm_.implementation = enumProp(p, "Implementation", kImplNames, 0);
+        prm_.ray_interval = p.getBool("RayInterval", true);
+        const std::string fmt = p.getString("depthFormat", "D32Float");
+        if (fmt == "D32FloatS8X24") prm_.use_stencil = 1;
+        else if (fmt == "D24UnormS8" || fmt == "D16Unorm")
+            throw Unsupported("StochasticDepthMap: depthFormat " + fmt + " (librsd stores 32-bit float depths: "
+                              "D32Float, or D32FloatS8X24 for the stencil)");
+        else if (fmt != "D32Float") throw std::runtime_error("StochasticDepthMap: depthFormat '" + fmt + "' is no depth format");
+        if (prm_.implementation == RSD_SD_RESERVOIR_SAMPLING || prm_.implementation == RSD_SD_KBUFFER)
+            throw Unsupported("StochasticDepthMap: Implementation must be Default or CoverageMask (ReservoirSampling "
+                              "depends on the fragment order)");
+    }
+    Reflection reflect(const CompileData&) override {
+        const uint32_t N = prm_.sample_count;
+        if (N != 1 && N != 2 && N != 4 && N != 8 && N != 16)  // kSampleCountList, StochasticDepthMap.cpp:56-63
+            throw Unsupported("StochasticDepthMap: Only 1, 2, 4, 8 and 16 samples are supported");
+        Reflection r;
+        r.addInput("depthMap", "non-linear (primary) depth map").format = Format::R32Float;
+        auto& st = r.addInput("stencilMask", "(optional) stencil-mask");
+        st.format = Format::R8Uint;
+        st.optional = true;
+        r.addInput("rayMin", "min ray T distance for depth values").optional = true;
+        r.addInput("rayMax", "max ray T distance for depth values").optional = true;
+        auto& o = r.addOutput("stochasticDepth", "stochastic depths in [0,1]");
+        o.format = N == 1 ? Format::R32Float : N == 2 ? Format::RG32Float : Format::RGBA32Float;
+        o.layers = (N + 3) / 4;
+        return r;
+    }
+    void setScene(Context&, const SceneRef* s) override { scene_ = s; }
+    void execute(Context& ctx, const RenderData& rd) override {
+        if (!scene_ || !scene_->scene) return;  // StochasticDepthMap.cpp:224
+        Texture* depth = rd["depthMap"];
+        Texture* sd = rd["stochasticDepth"];
+        Texture* mask = rd["stencilMask"];
+        Texture* rmin = rd["rayMin"];
+        Texture* rmax = rd["rayMax"];
+        if (depth->format != Format::R32Float) throw std::runtime_error("StochasticDepthMap: depthMap must be R32Float");
+        auto sized = [&](Texture* t, Format f, const char* n) {
+            if (t && (t->format != f || t->width != sd->width || t->height != sd->height))
+                throw std::runtime_error(std::string("StochasticDepthMap: ") + n + " must be " + formatName(f) +
+                                         " at the size of stochasticDepth");
+        };
+        sized(mask, Format::R8Uint, "stencilMask");
+        sized(rmin, Format::R32Uint, "rayMin");
+        sized(rmax, Format::R32Uint, "rayMax");
+        check(rsd_sd_raster(scene_->scene, &scene_->camera, &prm_, (const float*)depth->ptr, depth->width,
+                            depth->height, rmin ? (const uint32_t*)rmin->ptr : nullptr,
+                            rmax ? (const uint32_t*)rmax->ptr : nullptr, mask ? (const uint8_t*)mask->ptr : nullptr,
+                            (float*)sd->ptr, sd->width, sd->height, ctx.stream),
+              "StochasticDepthMap");
+    }
+
+private:
+    const SceneRef* scene_ = nullptr;
+    rsd_sd_raster_params prm_{};
+};
+
 // ------------------------------------------------------------------------------ SVAO
 // SVAO.cpp:73-100 Properties, :117-140 reflect, :143-190 compile (nested SD graph),
 // :192-455 execute.  Members the reference sets only from its GUI (SVAO.h:90-126) are
 // accepted as extra Properties with the same defaults: stochSamples, stochMaxCount,
-// stochGuardBand, stochJitter, rayInterval, cullMode, sampleCount, stochImplementation; and the
+// stochGuardBand, stochJitter, rayInterval, cullMode, sampleCount, stochImplementation, stochImpl
+// (mStochasticDepthImpl, SVAO.h:43-47, :112: "Ray", the default, or "Raster" -- the nested graph then holds
+// the raster StochasticDepthMap pass fed by gbufferDepth, without SD guard band and SD jitter); and the
 // librsd extensions stochHitOrder (rsd_hit_order, passed on as the SD pass's HitOrder) and numerics
 // ("Fast" / "Exact", rsd_numerics of the two SVAO passes; default RSD_NUMERICS from the environment, else Fast).
 class SVAOPass : public RenderPass {
@@ -553,6 +627,7 @@ public:
         cull_ = toRsdCull(enumProp(p, "cullMode", kCullNames, 2));
         directions_ = (uint32_t)p.getInt("sampleCount", 8);
         impl_ = enumProp(p, "stochImplementation", kImplNames, 0);
+        raster_ = enumProp(p, "stochImpl", {"Raster", "Ray"}, 1) == 0;  // SVAO.h:43-47
         hitOrder_ = enumProp(p, "stochHitOrder", kHitOrderNames, 0);  // librsd extension (rsd_hit_order)
         rayPipeline_ = p.getBool("rayPipeline", true);  // SVAO.h:101
         numerics_ = enumProp(p, "numerics", kNumericsNames, defaultNumerics());  // librsd extension (rsd_numerics)
@@ -571,13 +646,17 @@ public:
             throw Unsupported("SVAO: sampleCount must be 8, 16 or 32");
     }
     void sdSize(uint32_t w, uint32_t h, rsd_vao_data* vao, uint32_t* sw, uint32_t* sh) const {
-        // getExtraGuardBand (SVAO.cpp:718-723): only the StochasticDepth mode has an SD guard band
-        check(rsd_svao_make_vao_data(w, h, divisor_, secondary_ == 2 ? guardPx_ : 0, radius_, exponent_, thickness_, vao,
+        // getExtraGuardBand (SVAO.cpp:718-723): only the StochasticDepth mode with the ray-traced map has an SD
+        // guard band
+        check(rsd_svao_make_vao_data(w, h, divisor_, secondary_ == 2 && !raster_ ? guardPx_ : 0, radius_, exponent_, thickness_, vao,
                                      sw, sh),
               "SVAO");
     }
     Reflection reflect(const CompileData& cd) override {
         checkSupported();  // reported when the graph is planned, before any device work
+        // SVAO.cpp:368: the raster SD map's first layer is the G-buffer's non-linear depth
+        if (secondary_ == 2 && raster_ && cd.connected && !cd.connected->count("gbufferDepth"))
+            throw Unsupported("SVAO: stochImpl Raster needs 'gbufferDepth' (the non-linear G-buffer depth) connected");
         rsd_vao_data vao;
         uint32_t sw = 1, sh = 1;
         if (cd.defaultWidth && cd.defaultHeight) sdSize(cd.defaultWidth, cd.defaultHeight, &vao, &sw, &sh);
@@ -611,7 +690,8 @@ public:
         width_ = cd.defaultWidth;
         height_ = cd.defaultHeight;
         sdSize(width_, height_, &vao_, &sdW_, &sdH_);
-        svp_ = rsd_svao_params{directions_, samples_, secondary_, (uint32_t)rayInterval_, (uint32_t)jitter_, 0,
+        // SVAO.cpp:229: SD_JITTER only with the ray-traced map
+        svp_ = rsd_svao_params{directions_, samples_, secondary_, (uint32_t)rayInterval_, (uint32_t)(jitter_ && !raster_), 0,
                                (uint32_t)dualAo_, nullptr, numerics_, aoKernel_, primary_, nullptr};
         sdGraph_.reset();
         if (secondary_ != 2) return;
@@ -620,10 +700,19 @@ public:
         sd.set("SampleCount", (int64_t)samples_);
         sd.set("AlphaTest", alphaTest_);
         sd.set("Implementation", (int64_t)impl_);
-        sd.set("HitOrder", (int64_t)hitOrder_);
         sd.set("Alpha", (double)(float)(1.5 / samples_));
         sd.set("RayInterval", rayInterval_);
         sd.set("CullMode", std::string(cull_ == RSD_CULL_NONE ? "None" : cull_ == RSD_CULL_FRONT ? "Front" : "Back"));
+        if (raster_) {  // SVAO.cpp:171-176
+            sd.set("linearize", true);
+            sd.set("depthFormat", std::string("D32FloatS8X24"));
+            sdGraph_ = std::make_unique<RenderGraph>("Stochastic Depth");
+            sdGraph_->createPass("StochasticDepthMap", "StochasticDepthMap", sd);
+            sdGraph_->markOutput("StochasticDepthMap.stochasticDepth");
+            sdGraph_->setScene(ctx, scene_);
+            return;
+        }
+        sd.set("HitOrder", (int64_t)hitOrder_);
         sd.set("normalize", true);
         sd.set("StoreNormals", false);
         sd.set("Jitter", jitter_);
@@ -701,7 +790,15 @@ public:
             return;
         }
         // SVAO.cpp:364-390: the nested graph traces the stochastic depth map
-        sdGraph_->setInput("StochasticDepthMap.linearZ", depth);
+        if (raster_) {  // SVAO.cpp:367-369
+            Texture* nonLinear = rd["gbufferDepth"];
+            if (!nonLinear || nonLinear->format != Format::R32Float || nonLinear->width != width_ ||
+                nonLinear->height != height_)
+                throw std::runtime_error("SVAO: stochImpl Raster needs 'gbufferDepth' (R32Float, the frame size)");
+            sdGraph_->setInput("StochasticDepthMap.depthMap", nonLinear);
+        } else {
+            sdGraph_->setInput("StochasticDepthMap.linearZ", depth);
+        }
         sdGraph_->setInput("StochasticDepthMap.rayMin", rmin);
         sdGraph_->setInput("StochasticDepthMap.rayMax", rmax);
         sdGraph_->dictionary()["SD_CLEAR"] = false;
@@ -725,7 +822,7 @@ private:
     uint32_t primary_, secondary_, divisor_, samples_, maxCount_, cull_, directions_, impl_, hitOrder_, numerics_,
         aoKernel_ = 0;
     int32_t guardPx_;
-    bool dualAo_, alphaTest_, jitter_, rayInterval_, rayPipeline_;
+    bool dualAo_, alphaTest_, jitter_, rayInterval_, rayPipeline_, raster_ = false;
     uint32_t width_ = 0, height_ = 0, sdW_ = 0, sdH_ = 0;
     rsd_vao_data vao_{};
     rsd_svao_params svp_{};
@@ -1263,6 +1360,7 @@ void registerBuiltinPasses(PluginRegistry& r) {
     r.registerClass("DepthPeeling", "next depth layer behind a linear depth map", factory<DepthPeelingPass>());
     r.registerClass("RTAO", "ray-traced ambient occlusion (ground truth)", factory<RTAOPass>());
     r.registerClass("HBAO", "horizon-based AO over 16 deinterleaved quarter-size layers", factory<HBAOPass>());
+    r.registerClass("StochasticDepthMap", "rasterised stochastic depth map", factory<StochasticDepthMapPass>());
     r.registerClass("StochasticDepthMapRT", "ray-traced stochastic depth map", factory<StochasticDepthMapRTPass>());
     r.registerClass("SVAO", "stochastic-depth volumetric ambient occlusion", factory<SVAOPass>());
     r.registerClass("CrossBilateralBlur", "depth-aware cross bilateral blur", factory<CrossBilateralBlurPass>());

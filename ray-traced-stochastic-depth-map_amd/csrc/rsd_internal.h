@@ -93,6 +93,10 @@ namespace rsd {
 void set_error(const std::string& msg);
 rsd_status hip_fail(hipError_t e, const char* what);
 
+// sd_trace.hip: the stratified coverage-mask tables of N samples on HIP device `dev` (indices [N + 1], look-up
+// table [2^N]), uploaded once per (device, N) and never freed; shared by the SD trace and sd_raster.hip
+rsd_status sd_coverage_lut(int dev, uint32_t N, const int32_t** idx, const uint32_t** lut);
+
 // halo.hip: the sparse-halo steps with the band frame's options (csrc/band_frame.cpp).  ilv: interleaved
 // triples {texel, rayMin, rayMax} (a peer's prefix is one contiguous transfer); the SD lists then index
 // with stride 3 (their idx points at the triples).  row: a count row zeroed ([0, row_n)) with

@@ -2472,6 +2472,11 @@ rsd_status sd_workspace(rsd_scene* scene, hipStream_t s, SdWorkspace** out) {
 }
 
 rsd_status ensure_lut(int dev, uint32_t N, const int32_t** idx, const uint32_t** lut) {
+    return rsd::sd_coverage_lut(dev, N, idx, lut);
+}
+}  // namespace
+
+rsd_status rsd::sd_coverage_lut(int dev, uint32_t N, const int32_t** idx, const uint32_t** lut) {
     if (dev < 0 || dev >= kLutDevices || N > 16) {
         set_error("rsd_sd_trace: device index >= 64 or N > 16");
         return RSD_ERR_UNSUPPORTED;
@@ -2511,7 +2516,6 @@ rsd_status ensure_lut(int dev, uint32_t N, const int32_t** idx, const uint32_t**
     *lut = c.d_lut;
     return RSD_OK;
 }
-}  // namespace
 
 namespace {
 // The SD trace of the 8-row tile rows t = start + k * step, k < n (rsd_sd_trace_band_ex: an

@@ -74,6 +74,17 @@ class SDParams(C.Structure):
                 ("d_tile_state", C.c_void_p)]
 
 
+class SDRasterParams(C.Structure):  # rsd_sd_raster_params; the defaults of StochasticDepthMap.h
+    _fields_ = [("sample_count", C.c_uint32), ("alpha", C.c_float), ("cull_mode", C.c_uint32),
+                ("linearize", C.c_uint32), ("alpha_test", C.c_uint32), ("implementation", C.c_uint32),
+                ("ray_interval", C.c_uint32), ("use_stencil", C.c_uint32)]
+
+    def __init__(self, sample_count=8, alpha=0.2, cull_mode=CULL_BACK, linearize=True, alpha_test=True,
+                 implementation=SD_DEFAULT, ray_interval=True, use_stencil=False):
+        super().__init__(int(sample_count), float(alpha), int(cull_mode), int(linearize), int(alpha_test),
+                         int(implementation), int(ray_interval), int(use_stencil))
+
+
 class VAOData(C.Structure):
     _fields_ = [("noiseScale", C.c_float * 2), ("resolution", C.c_float * 2),
                 ("lowResolution", C.c_float * 2), ("invResolution", C.c_float * 2),
@@ -214,7 +225,7 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_band_frame_create", "rsd_band_frame_front", "rsd_band_frame_back", "rsd_band_frame_stats",
            "rsd_band_frame_release", "rsd_band_frame_set_split", "rsd_depth_peel", "rsd_gbuffer_world",
            "rsd_rtao", "rsd_rtao_sample_table", "rsd_rtao_ray_t_max", "rsd_rtao_pack", "rsd_hbao",
-           "rsd_hbao_noise_table"]
+           "rsd_hbao_noise_table", "rsd_sd_raster"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -380,6 +391,9 @@ def lib():
         L.rsd_hbao_noise_table.argtypes = [vp]
         L.rsd_depth_peel.restype = st
         L.rsd_depth_peel.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, f32, u32, vp, vp]
+        L.rsd_sd_raster.restype = st
+        L.rsd_sd_raster.argtypes = [vp, C.POINTER(Camera), C.POINTER(SDRasterParams), vp, u32, u32, vp, vp, vp, vp,
+                                    u32, u32, vp]
         L.rsd_linearize_depth.restype = st
         L.rsd_linearize_depth.argtypes = [vp, vp, u32, f32, f32, vp]
         L.rsd_compress_normals.restype = st

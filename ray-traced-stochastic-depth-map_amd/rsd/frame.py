@@ -460,6 +460,38 @@ class Renderer:
                                                  self.stream), "rsd_sd_trace_band_ex")
         return cnt
 
+    def sd_raster(self, **params):
+        """Fill self.sd with the RASTER stochastic depth map (rsd_sd_raster, the reference's StochasticDepthMap
+        pass as SVAO's StochasticDepthImpl::Raster runs it, SVAO.cpp:158-176) instead of sd_trace(): the first
+        layer is the non-linear depth that rsd_gbuffer_raster renders here with the config's cull mode (kept
+        as self.raster_depth), the intervals and the stencil are this renderer's ray_min / ray_max, so call it
+        after pass1(); pass2() can follow.  The raster map has no SD guard band and no SD jitter
+        (SVAO.cpp:229, :721) and pass 2 reads 32-bit maps.  params: abi.SDRasterParams members; the defaults
+        are the config's values with linearize, Alpha = 1.5 / N and the stencil on."""
+        cfg, t = self.cfg, self.torch
+        if self.vao.sdGuard != 0 or cfg.jitter:
+            raise ValueError("sd_raster(): the raster SD map has no guard band and no jitter "
+                             "(FrameConfig(sd_guard_px=0, jitter=False))")
+        if cfg.use_16bit:
+            raise ValueError("sd_raster(): the raster SD map is 32-bit (FrameConfig(use_16bit=False))")
+        prm = dict(sample_count=cfg.sd_samples, alpha=float(np.float32(1.5 / cfg.sd_samples)), cull_mode=cfg.cull_mode,
+                   linearize=True, alpha_test=cfg.alpha_test, implementation=cfg.implementation,
+                   ray_interval=cfg.ray_interval, use_stencil=True)
+        prm.update(params)
+        if prm["sample_count"] != cfg.sd_samples:
+            raise ValueError("sd_raster(): sample_count must be the config's sd_samples (the shape of self.sd)")
+        prm = abi.SDRasterParams(**prm)
+        W, H = cfg.fb_w, cfg.fb_h
+        self.raster_depth = t.empty((H, W), dtype=t.float32, device=self.depth.device)
+        normal_w = t.empty((H, W, 4), dtype=t.float32, device=self.depth.device)
+        abi.check(abi.lib().rsd_gbuffer_raster(self.gscene.h, C.byref(self.cam), W, H, cfg.cull_mode,
+                                               _ptr(self.raster_depth), _ptr(normal_w), self.stream),
+                  "rsd_gbuffer_raster")
+        abi.check(abi.lib().rsd_sd_raster(self.gscene.h, C.byref(self.cam), C.byref(prm), _ptr(self.raster_depth), W, H,
+                                          _ptr(self.ray_min), _ptr(self.ray_max), None, _ptr(self.sd), self.sd_w,
+                                          self.sd_h, self.stream), "rsd_sd_raster")
+        self.invalidate_sd_tiles()
+
     def pass2(self, band=(0, 1)):
         if self.cfg.use_16bit:  # SVAO never sets Use16Bit on its SD pass (SVAO.cpp:158-183)
             raise ValueError("SVAO pass 2 reads 32-bit SD maps; Use16Bit is a standalone SD-pass property")
