@@ -89,6 +89,38 @@ rsd_status rsd_cross_bilateral_blur_src(const uint8_t* d_src, uint32_t src_texel
                                         uint32_t z_w, uint32_t z_h, uint8_t* d_pingpong, uint8_t* d_dst,
                                         uint32_t width, uint32_t height, uint32_t guard_band, uint32_t kernel_radius,
                                         uint32_t better_slope, rsd_stream stream);
+/* AOGuidedBlur (AOGuidedBlur.ps.slang:105-208, AOGuidedBlur.cpp:121-173): resolves a (bright, dark) AO map into one
+ * AO value.  d_src: `layers` layers of qw x qh texels of src_texel_bytes bytes, RG8Unorm (2) or R8Unorm (1: dark
+ * reads 0); layers 16: qw x qh = ceil(width/4) x ceil(height/4) (rsd_deinterleave, rsd_hbao), layers 1: the frame
+ * itself.  d_depth_layers: the linear depth in the same shape, R32F.  The x pass writes (means, meansSq) into
+ * d_pingpong (RGBA8Unorm, 4 bytes per texel of d_src), the y pass the result into d_dst (R8Unorm); both write only
+ * inside the scissor guard_band / int(sqrt(layers) + 0.5) of each layer, while the taps are clamped to the
+ * guard band's uv bounds of the full-size width x height frame.  kernel_radius 1..20 (the pass's default 4);
+ * local_deviation 1 (the shader's default) weighs by |original - mean|, 0 by sqrt|meanSq - mean^2|. */
+typedef struct {
+    uint32_t kernel_radius;
+    uint32_t local_deviation;
+    uint32_t guard_band;
+    uint32_t width, height; /* the full-size frame */
+    uint32_t layers;        /* 1 or 16 */
+    uint32_t src_texel_bytes;
+} rsd_ao_guided_blur_params;
+rsd_status rsd_ao_guided_blur(const rsd_ao_guided_blur_params* params, const uint8_t* d_src,
+                              const float* d_depth_layers, uint8_t* d_pingpong, uint8_t* d_dst, rsd_stream stream);
+/* The AOGuidedBlur pass with enabled = False (AOGuidedBlur.cpp:130-138): the blit of the source into the R8Unorm
+ * output, byte 0 of each of the `texels` source texels (all layers, no scissor). */
+rsd_status rsd_ao_first_channel(const uint8_t* d_src, uint32_t src_texel_bytes, uint64_t texels, uint8_t* d_dst,
+                                rsd_stream stream);
+/* AOVarianceFix (AOVarianceFix.ps.slang:37-99, AOVarianceFix.cpp:115-159): the one-pass variant over the centre and
+ * its four cross neighbours, through a linear / clamp sampler (librsd's 8-bit sub-texel bilinear).  d_bright, d_dark
+ * and d_dst R8Unorm, d_depth_layers R32F, all `layers` layers shaped as above; the same scissor and uv bounds. */
+typedef struct {
+    uint32_t guard_band;
+    uint32_t width, height; /* the full-size frame */
+    uint32_t layers;        /* 1 or 16 */
+} rsd_ao_variance_fix_params;
+rsd_status rsd_ao_variance_fix(const rsd_ao_variance_fix_params* params, const uint8_t* d_bright,
+                               const uint8_t* d_dark, const float* d_depth_layers, uint8_t* d_dst, rsd_stream stream);
 /* RayMinMaxLength (RayMinMaxLength.ps.slang:4-16): the SD ray interval length per texel,
  * max(0, asfloat(rayMax) - asfloat(rayMin)) / 32, and 0 where rayMax is 0 (R32Float). */
 rsd_status rsd_ray_min_max_length(const uint32_t* d_ray_min, const uint32_t* d_ray_max, uint32_t width,

@@ -390,7 +390,9 @@ void RenderGraph::compile(Context& ctx, uint32_t width, uint32_t height, bool al
                 f.height = ext->second->height;
                 f.layers = ext->second->layers;
             }
-            if (f.fromSizeOnly) {
+            if (f.fromShapeOnly) {
+                f.format = declared;
+            } else if (f.fromSizeOnly) {
                 f.format = declared;
                 f.layers = 1;
             } else if (f.fromFormatOnly) {

@@ -80,6 +80,8 @@ struct Field {
     uint32_t shrink = 1, layersOut = 0;
     bool fromFormatOnly = false;
     bool fromSizeOnly = false;  // with formatFrom: copy the size, keep the declared format (RayMinMaxLength)
+    // with formatFrom: copy the size and the layer count, keep the declared format (AOGuidedBlur)
+    bool fromShapeOnly = false;
 };
 
 struct Reflection {

@@ -17,6 +17,8 @@
 //   HBAO                  HBAO.cpp                   rsd_hbao (16 deinterleaved layers in and out)
 //
 //   CrossBilateralBlur    CrossBilateralBlur.cpp     rsd_cross_bilateral_blur_src (R8Unorm or RG8Unorm in)
+//   AOGuidedBlur          AOGuidedBlur.cpp           rsd_ao_guided_blur (enabled = False: rsd_ao_first_channel)
+//   AOVarianceFix         AOVarianceFix.cpp          rsd_ao_variance_fix
 //   ImageEquation         ImageEquation.cpp          rsd_image_equation_compile / _run
 //   Switch                Switch.cpp                 copy of the selected input
 //   TemporalAO            TemporalAO.cpp             rsd_temporal_ao (enabled = False: copy)
@@ -895,6 +897,126 @@ private:
     void* pingpong_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------ AOGuidedBlur / AOVarianceFix
+// the guard band of the frame (the GuardBand pass's dictionary entry; 0 without one)
+uint32_t dictGuardBand(const RenderData& rd) {
+    auto& dict = rd.getDictionary();
+    auto it = dict.find("guardBand");
+    const int64_t g = it != dict.end() && std::holds_alternative<int64_t>(it->second) ? std::get<int64_t>(it->second) : 0;
+    return (uint32_t)(g > 0 ? g : 0);
+}
+
+// `t` is the frame itself (1 layer) or its 16 deinterleaved layers
+bool frameShaped(const Texture* t, uint32_t W, uint32_t H) {
+    if (t->layers == 1) return t->width == W && t->height == H;
+    return t->layers == 16 && t->width == (W + 3) / 4 && t->height == (H + 3) / 4;
+}
+
+// AOGuidedBlur.cpp:52-63 Properties (kernelRadius, clampResults, enabled), :83-109 reflect, :121-173 execute;
+// AOGuidedBlur.ps.slang.  ao2: the (bright, dark) map, RG8Unorm -- or R8Unorm, whose dark channel reads 0 -- as one
+// image or as the 16 layers DeinterleaveTexture and HBAO make; lineardepth in the same shape; color: R8Unorm in
+// the shape of ao2.  clampResults is accepted and ignored: its use is commented out in the shader (:155, :201).
+// mUseLocalDeviation is a GUI member in the reference (:182); librsd accepts it as the optional property
+// `localDeviation` (a librsd extension).  The RGBA8Unorm ping-pong image is the pass's own (:89).
+class AOGuidedBlurPass : public RenderPass {
+public:
+    explicit AOGuidedBlurPass(const Properties& p) {
+        props_ = p;
+        radius_ = (uint32_t)p.getInt("kernelRadius", 4);  // AOGuidedBlur.h:87-90
+        enabled_ = p.getBool("enabled", true);
+        localDeviation_ = p.getBool("localDeviation", true);
+        (void)p.getBool("clampResults", true);
+        if (radius_ < 1 || radius_ > 20) throw std::runtime_error("AOGuidedBlur: kernelRadius must be 1..20");
+    }
+    ~AOGuidedBlurPass() override { (void)hipFree(pingpong_); }
+    Reflection reflect(const CompileData&) override {
+        Reflection r;
+        r.addInput("ao2", "ao (bright, dark)").format = Format::RG8Unorm;  // the format a stub producer gets
+        r.addInput("lineardepth", "linear depth").format = Format::R32Float;
+        Field& o = r.addOutput("color", "blurred ao");
+        o.format = Format::R8Unorm;
+        o.formatFrom = "ao2";  // :93-103 the size and the array size of the input
+        o.fromShapeOnly = true;
+        return r;
+    }
+    void compile(Context&, const CompileData& cd) override {
+        (void)hipFree(pingpong_);
+        pingpong_ = nullptr;
+        // 16 layers of ceil(w/4) x ceil(h/4) hold at least the frame's texels
+        const size_t texels = (size_t)16 * ((cd.defaultWidth + 3) / 4) * ((cd.defaultHeight + 3) / 4);
+        if (enabled_ && hipMalloc(&pingpong_, texels * 4) != hipSuccess)
+            throw std::runtime_error("AOGuidedBlur: ping-pong allocation failed");
+    }
+    void execute(Context& ctx, const RenderData& rd) override {
+        Texture* in = rd["ao2"];
+        Texture* z = rd["lineardepth"];
+        Texture* out = rd["color"];
+        const uint32_t W = rd.defaultWidth(), H = rd.defaultHeight();
+        if (in->format != Format::RG8Unorm && in->format != Format::R8Unorm)
+            throw Unsupported("AOGuidedBlur: ao2 must be RG8Unorm or R8Unorm");
+        if (out->format != Format::R8Unorm || out->width != in->width || out->height != in->height ||
+            out->layers != in->layers)
+            throw std::runtime_error("AOGuidedBlur: color must be R8Unorm in the shape of ao2");
+        const uint32_t texelBytes = (uint32_t)formatBytes(in->format);
+        if (!enabled_) {  // :130-138
+            check(rsd_ao_first_channel((const uint8_t*)in->ptr, texelBytes, (uint64_t)in->width * in->height * in->layers,
+                                       (uint8_t*)out->ptr, ctx.stream),
+                  "AOGuidedBlur");
+            return;
+        }
+        if (!frameShaped(in, W, H))
+            throw Unsupported("AOGuidedBlur: ao2 must be the frame or its 16 layers of ceil(w/4) x ceil(h/4)");
+        if (z->format != Format::R32Float || z->width != in->width || z->height != in->height || z->layers != in->layers)
+            throw Unsupported("AOGuidedBlur: lineardepth must be R32Float in the shape of ao2");
+        const rsd_ao_guided_blur_params prm{radius_, localDeviation_ ? 1u : 0u, dictGuardBand(rd), W, H, in->layers,
+                                            texelBytes};
+        check(rsd_ao_guided_blur(&prm, (const uint8_t*)in->ptr, (const float*)z->ptr, (uint8_t*)pingpong_,
+                                 (uint8_t*)out->ptr, ctx.stream),
+              "AOGuidedBlur");
+    }
+
+private:
+    uint32_t radius_;
+    bool enabled_, localDeviation_;
+    void* pingpong_ = nullptr;
+};
+
+// AOVarianceFix.cpp:70-99 reflect (no properties), :115-159 execute; AOVarianceFix.ps.slang.  bright, dark: R8Unorm;
+// lineardepth: R32Float; color: the format and shape of bright.  mEnabled is a GUI member that starts true.
+class AOVarianceFixPass : public RenderPass {
+public:
+    explicit AOVarianceFixPass(const Properties& p) { props_ = p; }
+    Reflection reflect(const CompileData&) override {
+        Reflection r;
+        r.addInput("bright", "bright ao").format = Format::R8Unorm;
+        r.addInput("dark", "dark ao").format = Format::R8Unorm;
+        r.addInput("lineardepth", "linear depth").format = Format::R32Float;
+        Field& o = r.addOutput("color", "blurred ao");
+        o.format = Format::R8Unorm;
+        o.formatFrom = "bright";  // :83-93
+        return r;
+    }
+    void execute(Context& ctx, const RenderData& rd) override {
+        Texture* bright = rd["bright"];
+        Texture* dark = rd["dark"];
+        Texture* z = rd["lineardepth"];
+        Texture* out = rd["color"];
+        const uint32_t W = rd.defaultWidth(), H = rd.defaultHeight();
+        auto shaped = [&](const Texture* t, Format f) {
+            return t->format == f && t->width == bright->width && t->height == bright->height && t->layers == bright->layers;
+        };
+        if (bright->format != Format::R8Unorm || !frameShaped(bright, W, H))
+            throw Unsupported("AOVarianceFix: bright must be R8Unorm, the frame or its 16 layers of ceil(w/4) x ceil(h/4)");
+        if (!shaped(dark, Format::R8Unorm)) throw Unsupported("AOVarianceFix: dark must be R8Unorm in the shape of bright");
+        if (!shaped(z, Format::R32Float)) throw Unsupported("AOVarianceFix: lineardepth must be R32Float in the shape of bright");
+        if (!shaped(out, Format::R8Unorm)) throw std::runtime_error("AOVarianceFix: color must be shaped like bright");
+        const rsd_ao_variance_fix_params prm{dictGuardBand(rd), W, H, bright->layers};
+        check(rsd_ao_variance_fix(&prm, (const uint8_t*)bright->ptr, (const uint8_t*)dark->ptr, (const float*)z->ptr,
+                                  (uint8_t*)out->ptr, ctx.stream),
+              "AOVarianceFix");
+    }
+};
+
 // ------------------------------------------------------------------------------ ImageEquation
 // ImageEquation.cpp:43-160: `formula` (default "I0[xy]"), `format` (default RGBA32Float).  An
 // invalid formula leaves the pass invalid (execute does nothing), as in the reference.
@@ -1364,6 +1486,8 @@ void registerBuiltinPasses(PluginRegistry& r) {
     r.registerClass("StochasticDepthMapRT", "ray-traced stochastic depth map", factory<StochasticDepthMapRTPass>());
     r.registerClass("SVAO", "stochastic-depth volumetric ambient occlusion", factory<SVAOPass>());
     r.registerClass("CrossBilateralBlur", "depth-aware cross bilateral blur", factory<CrossBilateralBlurPass>());
+    r.registerClass("AOGuidedBlur", "depth-guided blur resolving a (bright, dark) AO map", factory<AOGuidedBlurPass>());
+    r.registerClass("AOVarianceFix", "one-pass 5-tap resolve of separate bright and dark AO", factory<AOVarianceFixPass>());
     r.registerClass("ImageEquation", "per-pixel formula over up to 4 images", factory<ImageEquationPass>());
     r.registerClass("Switch", "forwards the selected input", factory<SwitchPass>());
     r.registerClass("TemporalAO", "temporal AO accumulation over motion vectors", factory<TemporalAOPass>());

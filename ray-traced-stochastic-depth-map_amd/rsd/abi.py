@@ -137,6 +137,24 @@ class HBAOParams(C.Structure):  # rsd_hbao_params; the defaults of HBAOData.slan
                 self.rand[i][:] = [float(v) for v in row]
 
 
+class AOGuidedBlurParams(C.Structure):  # rsd_ao_guided_blur_params (rsd_graph.h); the defaults of AOGuidedBlur.h
+    _fields_ = [("kernel_radius", C.c_uint32), ("local_deviation", C.c_uint32), ("guard_band", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("layers", C.c_uint32), ("src_texel_bytes", C.c_uint32)]
+
+    def __init__(self, width=0, height=0, layers=16, src_texel_bytes=2, kernel_radius=4, local_deviation=True,
+                 guard_band=0):
+        """width, height: the full-size frame; layers: 16 (deinterleaved) or 1 (the frame itself)."""
+        super().__init__(int(kernel_radius), int(local_deviation), int(guard_band), int(width), int(height), int(layers),
+                         int(src_texel_bytes))
+
+
+class AOVarianceFixParams(C.Structure):  # rsd_ao_variance_fix_params (rsd_graph.h)
+    _fields_ = [("guard_band", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("layers", C.c_uint32)]
+
+    def __init__(self, width=0, height=0, layers=16, guard_band=0):
+        super().__init__(int(guard_band), int(width), int(height), int(layers))
+
+
 class HaloRegion(C.Structure):  # rsd_halo_region
     _fields_ = [("row0", C.c_uint32), ("row1", C.c_uint32), ("out", C.c_void_p), ("stride", C.c_uint32),
                 ("period", C.c_uint32), ("count", C.c_void_p)]
@@ -240,7 +258,7 @@ GRAPH_EXPORTS = ["rsd_graph_create", "rsd_graph_destroy", "rsd_graph_create_pass
                  "rsd_image_equation_run", "rsd_image_equation_release", "rsd_temporal_ao",
                  "rsd_motion_vectors", "rsd_motion_vectors_raster", "rsd_taa", "rsd_ao_flicker_mask", "rsd_binary_dilation",
                  "rsd_deinterleave", "rsd_interleave", "rsd_ray_min_max_length", "rsd_temporal_depth_peel",
-                 "rsd_cross_bilateral_blur_src"]
+                 "rsd_cross_bilateral_blur_src", "rsd_ao_guided_blur", "rsd_ao_first_channel", "rsd_ao_variance_fix"]
 
 FMT_R32F, FMT_RG32F, FMT_RGBA32F, FMT_R16U, FMT_R8U, FMT_R8UNORM, FMT_R32U, FMT_UNKNOWN = range(8)
 FMT_R16F, FMT_RG16F, FMT_RGBA16F, FMT_RG8UNORM = 8, 9, 10, 11
@@ -426,6 +444,12 @@ def lib():
         L.rsd_cross_bilateral_blur.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp]
         L.rsd_cross_bilateral_blur_src.restype = st
         L.rsd_cross_bilateral_blur_src.argtypes = [vp, u32, vp, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp]
+        L.rsd_ao_guided_blur.restype = st
+        L.rsd_ao_guided_blur.argtypes = [C.POINTER(AOGuidedBlurParams), vp, vp, vp, vp, vp]
+        L.rsd_ao_first_channel.restype = st
+        L.rsd_ao_first_channel.argtypes = [vp, u32, C.c_uint64, vp, vp]
+        L.rsd_ao_variance_fix.restype = st
+        L.rsd_ao_variance_fix.argtypes = [C.POINTER(AOVarianceFixParams), vp, vp, vp, vp, vp]
         L.rsd_temporal_ao.restype = st
         L.rsd_temporal_ao.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, C.POINTER(Camera), vp, vp, vp, vp]
         L.rsd_temporal_depth_peel.restype = st

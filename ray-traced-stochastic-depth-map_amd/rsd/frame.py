@@ -433,6 +433,58 @@ class Renderer:
         abi.check(L.rsd_interleave(_ptr(ambient_layers), W, H, 2, _ptr(ambient), self.stream), "rsd_interleave")
         return ambient
 
+    def _frame_layers(self, image, name, dtype):
+        """`image`, a frame-size tensor of 1-, 2- or 4-byte texels, as the 16 layers of rsd_deinterleave."""
+        t, W, H = self.torch, self.cfg.fb_w, self.cfg.fb_h
+        if image is None or tuple(image.shape[:2]) != (H, W) or image.dtype != dtype:
+            raise ValueError(f"{name} must be a {dtype} tensor of the frame size")
+        image = image.contiguous()
+        layers = t.empty((16, (H + 3) // 4, (W + 3) // 4) + tuple(image.shape[2:]), dtype=dtype, device=image.device)
+        abi.check(abi.lib().rsd_deinterleave(_ptr(image), W, H, image.element_size() * int(np.prod(image.shape[2:])),
+                                             _ptr(layers), self.stream), "rsd_deinterleave")
+        return layers
+
+    def ao_guided_blur(self, ao2=None, kernel_radius: int = 4, local_deviation: bool = True, guard_band=None):
+        """The dual AO map resolved into one AO value (rsd_ao_guided_blur, the reference's AOGuidedBlur pass with
+        its DeinterleaveTexture / InterleaveTexture neighbours): ao2 -- default self.ao, the (bright, dark) map of a
+        dual_ao config; a frame-size uint8 tensor x 2, or without the last axis (dark then reads 0) -- and
+        self.depth are deinterleaved into 16 quarter-size layers, blurred in x and y under the depth's guidance
+        and interleaved back.  guard_band defaults to the config's.  Returns the AO, a uint8 tensor of the frame
+        size; texels outside the guard-band scissor read 0."""
+        t, L, W, H = self.torch, abi.lib(), self.cfg.fb_w, self.cfg.fb_h
+        ao2 = self.ao if ao2 is None else ao2
+        if ao2 is not None and ao2.dim() == 3 and ao2.shape[2] != 2:
+            raise ValueError("ao2 must be a uint8 tensor of the frame size, x 2 for (bright, dark)")
+        src = self._frame_layers(ao2, "ao2", t.uint8)
+        depth = self._frame_layers(self.depth, "depth", t.float32)
+        prm = abi.AOGuidedBlurParams(W, H, 16, 2 if src.dim() == 4 else 1, kernel_radius, local_deviation,
+                                     self.cfg.guard_band if guard_band is None else guard_band)
+        pingpong = t.empty(tuple(depth.shape) + (4,), dtype=t.uint8, device=depth.device)
+        out_layers = t.zeros(tuple(depth.shape), dtype=t.uint8, device=depth.device)
+        abi.check(L.rsd_ao_guided_blur(C.byref(prm), _ptr(src), _ptr(depth), _ptr(pingpong), _ptr(out_layers),
+                                       self.stream), "rsd_ao_guided_blur")
+        out = t.empty((H, W), dtype=t.uint8, device=depth.device)
+        abi.check(L.rsd_interleave(_ptr(out_layers), W, H, 1, _ptr(out), self.stream), "rsd_interleave")
+        return out
+
+    def ao_variance_fix(self, bright, dark, guard_band=None):
+        """The one-pass variant (rsd_ao_variance_fix, the reference's AOVarianceFix pass between its
+        DeinterleaveTexture and InterleaveTexture neighbours): bright and dark, uint8 tensors of the frame size,
+        and self.depth go through 16 quarter-size layers.  Returns the AO like ao_guided_blur."""
+        t, L, W, H = self.torch, abi.lib(), self.cfg.fb_w, self.cfg.fb_h
+        for name, image in (("bright", bright), ("dark", dark)):
+            if image is None or image.dim() != 2:
+                raise ValueError(f"{name} must be a uint8 tensor of the frame size")
+        b, d = self._frame_layers(bright, "bright", t.uint8), self._frame_layers(dark, "dark", t.uint8)
+        depth = self._frame_layers(self.depth, "depth", t.float32)
+        prm = abi.AOVarianceFixParams(W, H, 16, self.cfg.guard_band if guard_band is None else guard_band)
+        out_layers = t.zeros(tuple(depth.shape), dtype=t.uint8, device=depth.device)
+        abi.check(L.rsd_ao_variance_fix(C.byref(prm), _ptr(b), _ptr(d), _ptr(depth), _ptr(out_layers), self.stream),
+                  "rsd_ao_variance_fix")
+        out = t.empty((H, W), dtype=t.uint8, device=depth.device)
+        abi.check(L.rsd_interleave(_ptr(out_layers), W, H, 1, _ptr(out), self.stream), "rsd_interleave")
+        return out
+
     def clear_intervals(self):
         abi.check(abi.lib().rsd_svao_clear_intervals(_ptr(self.ray_min), _ptr(self.ray_max), self.sd_w * self.sd_h,
                                                      self.stream), "rsd_svao_clear_intervals")
