@@ -186,13 +186,72 @@ rsd_status rsd_motion_vectors_raster(const rsd_camera* cam, const rsd_camera* pr
 /* ImageEquation (ImageEquation.cpp:134-160, ImageEquation.ps.slang): `formula` is the HLSL
  * expression of `float4 result = (FORMULA)` over I0..I3[xy].  Compile on the host (syntax
  * errors -> RSD_ERR_INVALID_ARG, message in rsd_last_error), run on a stream: inputs[4]
- * (ptr NULL = unbound), output RGBA32F / RG32F / R32F / R8Unorm. */
+ * (ptr NULL = unbound; any rsd_format but the 16-bit float ones), output RGBA32F / RG32F / R32F / R8Unorm. */
 typedef struct rsd_image_program rsd_image_program;
 rsd_status rsd_image_equation_compile(const char* formula, rsd_image_program** out);
 rsd_status rsd_image_equation_info(const rsd_image_program* prog, uint32_t* instructions, uint32_t* texture_mask);
 rsd_status rsd_image_equation_run(const rsd_image_program* prog, const rsd_texture* inputs, const rsd_texture* out,
                                   rsd_stream stream);
 void rsd_image_equation_release(rsd_image_program* prog);
+
+/* ConvolutionalNet (ConvolutionNet.h:115-231, ConvolutionalNet.cpp:131-235): the learned resolve of the (bright, dark)
+ * AO pair -- a small convolutional net per array slice over four single-channel images (bright, dark, importance,
+ * depth: channels 0..3 of the first layer), ReLU between the layers, the last layer's channel 0 clamped into
+ * [dark, bright].  A net is 1..8 layers for each of `slices` (1 or 16) slices; every slice has its own weights but
+ * the same layer count, kernel sizes and channel counts (RSD_ERR_UNSUPPORTED otherwise, as for a kernel size outside
+ * 1..7, more than 32 channels, more than 4 input channels or channels_in[l] != channels_out[l - 1]).
+ * weights: [slices][K][K][Cin][Cout] with axis 0 the x offset: w[a][b] applies at (x + a - K/2, y + b - K/2), the
+ * transpose of the Keras layout (what Matrix::get indexes, ConvolutionNet.h:16-24).  A tap outside the image reads 0.
+ * rsd_convnet_create takes the arrays as they are; rsd_convnet_load_dir reads the reference's file layout,
+ * <dir>/<slice>_weight_<l>.npy ('<f4' [K][K][Cin][Cout]) and <slice>_bias_<l>.npy ([Cout]; a missing file: zeros) for
+ * l = 0.. until no weight file exists, and rounds every value to (float)strtod of its "%g" text: the reference
+ * prints its weights into shader text with operator<<(float).  Both are host-only; the first rsd_convnet_run on a
+ * device uploads the weights to it with hipMalloc and a synchronous hipMemcpy, so that first run must not sit inside a
+ * stream capture: run the net once before capturing.  Later runs on that device only launch kernels.  Runs of one
+ * net may come from several host threads; rsd_convnet_release frees the uploads and must be the net's last call, with
+ * no run in flight on another thread. */
+typedef struct rsd_convnet rsd_convnet;
+typedef struct {
+    uint32_t kernel, channels_in, channels_out;
+    const float* weights; /* [slices][K][K][Cin][Cout] */
+    const float* bias;    /* [slices][Cout] or NULL = zeros */
+} rsd_convnet_layer;
+rsd_status rsd_convnet_create(const rsd_convnet_layer* layers, uint32_t layer_count, uint32_t slices,
+                              rsd_convnet** out);
+rsd_status rsd_convnet_load_dir(const char* dir, uint32_t slices, rsd_convnet** out);
+void rsd_convnet_release(rsd_convnet* net);
+typedef struct {
+    uint32_t layers, slices;
+    uint32_t radius; /* sum of the layers' K / 2: how far the output depends on the inputs */
+    uint32_t fused;  /* 1: a Float-precision run takes the fused kernel (its LDS footprint fits), 0: one launch per layer */
+    uint32_t kernel[8], channels_in[8], channels_out[8];
+} rsd_convnet_info;
+rsd_status rsd_convnet_get_info(const rsd_convnet* net, rsd_convnet_info* info);
+enum { RSD_CONVNET_FLOAT = 0, RSD_CONVNET_HALF = 1, RSD_CONVNET_UNORM = 2 }; /* rsd_convnet_params.precision */
+/* One run.  The four inputs are `layers` layers (16: ceil(width/4) x ceil(height/4) each, 1: the frame itself) of
+ * in_texel_bytes[i] = 1 (R8Unorm, byte / 255) or 4 (R32Float) bytes per texel; only the first channels_in[0] are read
+ * (and bright and dark by the clamp), the others may be NULL.  d_out: R32Float in the same shape.  Every layer draws
+ * only inside the scissor guard_band / int(sqrt(layers) + 0.5) of each layer (rsd_ao_guided_blur's): output texels
+ * outside keep what d_out held, intermediate texels outside read 0, the inputs are read wherever the image has them.
+ * precision: how an intermediate is stored between layers -- unchanged, as binary16 (round to nearest even) or as
+ * R8Unorm.  clamp_output 1: min(max(v, dark), bright) (a NaN gives dark, dark > bright gives bright), 0: v.
+ * numerics: RSD_NUMERICS_EXACT rounds every multiply and add separately in the reference's order (bias, then input
+ * channels -- in groups of 4 after the first layer --, then y, then x, then the channel of the group); the zero
+ * default RSD_NUMERICS_FAST may fuse and applies to Float only: Half and UNorm always run the exact arithmetic.
+ * d_scratch: rsd_convnet_scratch_bytes bytes (may be NULL when that is 0); layer l < layers - 1 of the net keeps its
+ * activations there as [slices][Cout][h][w] planes, one 256-byte-aligned block per layer in order, when the
+ * per-layer kernels run.  RSD_CONVNET_FUSED=off in the environment (read by every run) forces those kernels. */
+typedef struct {
+    uint32_t width, height; /* the full-size frame */
+    uint32_t guard_band;
+    uint32_t layers;        /* 1 or 16, == the net's slices */
+    uint32_t precision, clamp_output, numerics;
+    uint32_t in_texel_bytes[4];
+} rsd_convnet_params;
+uint64_t rsd_convnet_scratch_bytes(const rsd_convnet* net, const rsd_convnet_params* params);
+rsd_status rsd_convnet_run(rsd_convnet* net, const rsd_convnet_params* params, const void* d_bright,
+                           const void* d_dark, const void* d_importance, const void* d_depth, void* d_scratch,
+                           float* d_out, rsd_stream stream);
 
 /* plugin registry */
 rsd_status rsd_plugin_set_dir(const char* dir);

@@ -19,6 +19,7 @@
 //   CrossBilateralBlur    CrossBilateralBlur.cpp     rsd_cross_bilateral_blur_src (R8Unorm or RG8Unorm in)
 //   AOGuidedBlur          AOGuidedBlur.cpp           rsd_ao_guided_blur (enabled = False: rsd_ao_first_channel)
 //   AOVarianceFix         AOVarianceFix.cpp          rsd_ao_variance_fix
+//   ConvolutionalNet      ConvolutionalNet.cpp       rsd_convnet_load_dir / _run (the learned resolve)
 //   ImageEquation         ImageEquation.cpp          rsd_image_equation_compile / _run
 //   Switch                Switch.cpp                 copy of the selected input
 //   TemporalAO            TemporalAO.cpp             rsd_temporal_ao (enabled = False: copy)
@@ -1017,6 +1018,105 @@ public:
     }
 };
 
+// ------------------------------------------------------------------------------ ConvolutionalNet
+// ConvolutionalNet.cpp:48-68 constructor (one net per slice from the NeuralNet data directory), :75-117 reflect,
+// :131-235 execute; ConvolutionNet.h.  bright, dark, importance, depth: single-channel images, R8Unorm or R32Float,
+// in the shape of bright (the 16 layers of DeinterleaveTexture, or one image); only those the first layer reads (and
+// bright and dark for the clamp) must hold data at execute.  out: R32Float in the shape of bright.  The reference
+// takes no properties; librsd's extensions: `weights` (the directory, default the environment's RSD_NEURALNET_DIR),
+// `precision` ("Float" / "Half" / "UNorm": mPrecision, a GUI dropdown), `clampOutput` (mClampOutput, a GUI checkbox,
+// default true) and `numerics` as the SVAO pass.  Without a directory the pass constructs, reflects and plans -- the
+// reference scripts load unchanged -- and refuses to compile.  RSD_CONVNET_FUSED is read by every rsd_convnet_run.
+// The intermediates (the reference's i<layer>_s<slice> outputs) are the pass's own scratch.
+const std::initializer_list<const char*> kConvPrecisionNames = {"Float", "Half", "UNorm"};  // ConvolutionNet::Precision
+class ConvolutionalNetPass : public RenderPass {
+public:
+    explicit ConvolutionalNetPass(const Properties& p) {
+        props_ = p;
+        const char* env = std::getenv("RSD_NEURALNET_DIR");
+        dir_ = p.getString("weights", env ? env : "");
+        precision_ = enumProp(p, "precision", kConvPrecisionNames, RSD_CONVNET_FLOAT);
+        if (precision_ > RSD_CONVNET_UNORM) throw std::runtime_error("ConvolutionalNet: precision must be Float, Half or UNorm");
+        clamp_ = p.getBool("clampOutput", true);
+        numerics_ = enumProp(p, "numerics", kNumericsNames, defaultNumerics());
+        if (numerics_ > RSD_NUMERICS_EXACT) throw std::runtime_error("ConvolutionalNet: numerics must be Fast or Exact");
+        if (!dir_.empty()) check(rsd_convnet_load_dir(dir_.c_str(), 16, &net_), "ConvolutionalNet");
+    }
+    ~ConvolutionalNetPass() override {
+        (void)hipFree(scratch_);
+        rsd_convnet_release(net_);
+    }
+    Reflection reflect(const CompileData&) override {
+        Reflection r;
+        r.addInput("bright", "Channel 1").format = Format::R8Unorm;  // the formats a stub producer gets
+        r.addInput("dark", "Channel 2").format = Format::R8Unorm;
+        Field& imp = r.addInput("importance", "Channel 3");
+        imp.format = Format::R8Unorm;
+        imp.optional = true;
+        Field& z = r.addInput("depth", "Channel 4");
+        z.format = Format::R32Float;
+        z.optional = true;
+        Field& o = r.addOutput("out", "Output");
+        o.format = Format::R32Float;  // :85
+        o.formatFrom = "bright";      // :89-96 the size of the input, its slices
+        o.fromShapeOnly = true;
+        return r;
+    }
+    void compile(Context&, const CompileData&) override {
+        if (!net_)
+            throw std::runtime_error("ConvolutionalNet: no network loaded (set the 'weights' property or RSD_NEURALNET_DIR)");
+        (void)hipFree(scratch_);
+        scratch_ = nullptr;
+        scratchBytes_ = 0;
+    }
+    void execute(Context& ctx, const RenderData& rd) override {
+        if (!net_) throw std::runtime_error("ConvolutionalNet: no network loaded");
+        Texture* in[4] = {rd["bright"], rd["dark"], rd["importance"], rd["depth"]};
+        Texture* out = rd["out"];
+        const uint32_t W = rd.defaultWidth(), H = rd.defaultHeight();
+        rsd_convnet_info info{};
+        check(rsd_convnet_get_info(net_, &info), "ConvolutionalNet");
+        if (!in[0] || !frameShaped(in[0], W, H))
+            throw Unsupported("ConvolutionalNet: bright must be the frame or its 16 layers of ceil(w/4) x ceil(h/4)");
+        rsd_convnet_params prm{W, H, dictGuardBand(rd), in[0]->layers, precision_, clamp_ ? 1u : 0u, numerics_, {1, 1, 1, 4}};
+        const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+        static const char* kNames[4] = {"bright", "dark", "importance", "depth"};
+        for (uint32_t c = 0; c < 4; ++c) {
+            const bool needed = c < info.channels_in[0] || (c < 2 && clamp_);
+            if (!in[c] || !in[c]->ptr) {
+                if (needed) throw std::runtime_error(std::string("ConvolutionalNet: the net reads '") + kNames[c] + "', which is not connected");
+                continue;
+            }
+            if ((in[c]->format != Format::R8Unorm && in[c]->format != Format::R32Float) || in[c]->width != in[0]->width ||
+                in[c]->height != in[0]->height || in[c]->layers != in[0]->layers)
+                throw Unsupported(std::string("ConvolutionalNet: ") + kNames[c] + " must be R8Unorm or R32Float in the shape of bright");
+            prm.in_texel_bytes[c] = (uint32_t)formatBytes(in[c]->format);
+            ptr[c] = in[c]->ptr;
+        }
+        if (out->format != Format::R32Float || out->width != in[0]->width || out->height != in[0]->height ||
+            out->layers != in[0]->layers)
+            throw std::runtime_error("ConvolutionalNet: out must be R32Float in the shape of bright");
+        const uint64_t need = rsd_convnet_scratch_bytes(net_, &prm);
+        if (need > scratchBytes_) {
+            (void)hipFree(scratch_);
+            scratch_ = nullptr;
+            scratchBytes_ = 0;
+            if (hipMalloc(&scratch_, need) != hipSuccess) throw std::runtime_error("ConvolutionalNet: scratch allocation failed");
+            scratchBytes_ = need;
+        }
+        check(rsd_convnet_run(net_, &prm, ptr[0], ptr[1], ptr[2], ptr[3], scratch_, (float*)out->ptr, ctx.stream),
+              "ConvolutionalNet");
+    }
+
+private:
+    std::string dir_;
+    uint32_t precision_, numerics_;
+    bool clamp_;
+    rsd_convnet* net_ = nullptr;
+    void* scratch_ = nullptr;
+    uint64_t scratchBytes_ = 0;
+};
+
 // ------------------------------------------------------------------------------ ImageEquation
 // ImageEquation.cpp:43-160: `formula` (default "I0[xy]"), `format` (default RGBA32Float).  An
 // invalid formula leaves the pass invalid (execute does nothing), as in the reference.
@@ -1428,7 +1528,9 @@ public:
     void execute(Context& ctx, const RenderData& rd) override {
         Texture* in = rd["texIn"];
         Texture* out = rd["texOut"];
-        if (in->layers == 1) return;  // fed by a stub pass (e.g. ConvolutionalNet): no data to interleave
+        // fed by a stub pass (a pass type outside librsd, whose output is one placeholder layer): no data to
+        // interleave.  ConvolutionalNet, once the usual case, is a real pass now and feeds 16 layers.
+        if (in->layers == 1) return;
         if (in->layers != 16 || in->format != out->format || in->width != (out->width + 3) / 4 ||
             in->height != (out->height + 3) / 4)
             throw Unsupported("InterleaveTexture: input must be 16 layers of ceil(w/4) x ceil(h/4) of the output");
@@ -1488,6 +1590,7 @@ void registerBuiltinPasses(PluginRegistry& r) {
     r.registerClass("CrossBilateralBlur", "depth-aware cross bilateral blur", factory<CrossBilateralBlurPass>());
     r.registerClass("AOGuidedBlur", "depth-guided blur resolving a (bright, dark) AO map", factory<AOGuidedBlurPass>());
     r.registerClass("AOVarianceFix", "one-pass 5-tap resolve of separate bright and dark AO", factory<AOVarianceFixPass>());
+    r.registerClass("ConvolutionalNet", "per-slice convolutional net resolving bright and dark AO", factory<ConvolutionalNetPass>());
     r.registerClass("ImageEquation", "per-pixel formula over up to 4 images", factory<ImageEquationPass>());
     r.registerClass("Switch", "forwards the selected input", factory<SwitchPass>());
     r.registerClass("TemporalAO", "temporal AO accumulation over motion vectors", factory<TemporalAOPass>());

@@ -489,6 +489,10 @@ __device__ __forceinline__ float4 load_texel(const TexDesc& t, int x, int y) {
         case RSD_FMT_R8U: return make_float4((float)static_cast<const uint8_t*>(t.ptr)[o], 0.0f, 0.0f, 1.0f);
         case RSD_FMT_R16U: return make_float4((float)static_cast<const uint16_t*>(t.ptr)[o], 0.0f, 0.0f, 1.0f);
         case RSD_FMT_R32U: return make_float4((float)static_cast<const uint32_t*>(t.ptr)[o], 0.0f, 0.0f, 1.0f);
+        case RSD_FMT_RG8UNORM: {  // SVAO's dualAO map: ExtractBright / ExtractDark of scripts/SAVO_record.py read it
+            const uchar2 v = static_cast<const uchar2*>(t.ptr)[o];
+            return make_float4(unorm8_to_float(v.x), unorm8_to_float(v.y), 0.0f, 1.0f);
+        }
         default: return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 }
@@ -893,7 +897,7 @@ extern "C" rsd_status rsd_image_equation_run(const rsd_image_program* prog, cons
     a.prog = image_program(prog);
     for (int k = 0; k < 4; ++k) {
         if (inputs && inputs[k].ptr) {
-            if (inputs[k].format >= RSD_FMT_UNKNOWN) {
+            if (inputs[k].format >= RSD_FMT_UNKNOWN && inputs[k].format != RSD_FMT_RG8UNORM) {
                 set_error("rsd_image_equation_run: input of unknown format");
                 return RSD_ERR_INVALID_ARG;
             }

@@ -155,6 +155,34 @@ class AOVarianceFixParams(C.Structure):  # rsd_ao_variance_fix_params (rsd_graph
         super().__init__(int(guard_band), int(width), int(height), int(layers))
 
 
+class ConvNetLayer(C.Structure):  # rsd_convnet_layer (rsd_graph.h)
+    _fields_ = [("kernel", C.c_uint32), ("channels_in", C.c_uint32), ("channels_out", C.c_uint32),
+                ("weights", C.c_void_p), ("bias", C.c_void_p)]
+
+
+class ConvNetInfo(C.Structure):  # rsd_convnet_info
+    _fields_ = [("layers", C.c_uint32), ("slices", C.c_uint32), ("radius", C.c_uint32), ("fused", C.c_uint32),
+                ("kernel", C.c_uint32 * 8), ("channels_in", C.c_uint32 * 8), ("channels_out", C.c_uint32 * 8)]
+
+
+CONVNET_FLOAT, CONVNET_HALF, CONVNET_UNORM = 0, 1, 2  # rsd_convnet_params.precision
+CONVNET_PRECISIONS = {"Float": CONVNET_FLOAT, "Half": CONVNET_HALF, "UNorm": CONVNET_UNORM}
+
+
+class ConvNetParams(C.Structure):  # rsd_convnet_params; the defaults of ConvolutionalNet.h (Float, clamped)
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("guard_band", C.c_uint32), ("layers", C.c_uint32),
+                ("precision", C.c_uint32), ("clamp_output", C.c_uint32), ("numerics", C.c_uint32),
+                ("in_texel_bytes", C.c_uint32 * 4)]
+
+    def __init__(self, width=0, height=0, layers=16, guard_band=0, precision=CONVNET_FLOAT, clamp_output=True,
+                 numerics=0, in_texel_bytes=(1, 1, 1, 4)):
+        """width, height: the full-size frame; layers: 16 (deinterleaved) or 1 (the frame itself); in_texel_bytes:
+        of bright, dark, importance, depth -- scripts/SAVO_record.py feeds R8Unorm x 3 and R32Float."""
+        precision = CONVNET_PRECISIONS.get(precision, precision)
+        super().__init__(int(width), int(height), int(guard_band), int(layers), int(precision), int(clamp_output),
+                         int(numerics), (C.c_uint32 * 4)(*[int(b) for b in in_texel_bytes]))
+
+
 class HaloRegion(C.Structure):  # rsd_halo_region
     _fields_ = [("row0", C.c_uint32), ("row1", C.c_uint32), ("out", C.c_void_p), ("stride", C.c_uint32),
                 ("period", C.c_uint32), ("count", C.c_void_p)]
@@ -248,7 +276,8 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
 
-# every symbol include/rsd_graph.h declares
+# every symbol include/rsd_graph.h declares with an rsd_status or void result (rsd_convnet_scratch_bytes returns a
+# byte count: GRAPH_SIZE_EXPORTS)
 GRAPH_EXPORTS = ["rsd_graph_create", "rsd_graph_destroy", "rsd_graph_create_pass", "rsd_graph_add_edge",
                  "rsd_graph_mark_output", "rsd_graph_set_scene", "rsd_graph_set_input", "rsd_graph_compile",
                  "rsd_graph_execute", "rsd_graph_plan", "rsd_graph_resources", "rsd_graph_get_output",
@@ -258,7 +287,10 @@ GRAPH_EXPORTS = ["rsd_graph_create", "rsd_graph_destroy", "rsd_graph_create_pass
                  "rsd_image_equation_run", "rsd_image_equation_release", "rsd_temporal_ao",
                  "rsd_motion_vectors", "rsd_motion_vectors_raster", "rsd_taa", "rsd_ao_flicker_mask", "rsd_binary_dilation",
                  "rsd_deinterleave", "rsd_interleave", "rsd_ray_min_max_length", "rsd_temporal_depth_peel",
-                 "rsd_cross_bilateral_blur_src", "rsd_ao_guided_blur", "rsd_ao_first_channel", "rsd_ao_variance_fix"]
+                 "rsd_cross_bilateral_blur_src", "rsd_ao_guided_blur", "rsd_ao_first_channel", "rsd_ao_variance_fix",
+                 "rsd_convnet_create", "rsd_convnet_load_dir", "rsd_convnet_release", "rsd_convnet_get_info",
+                 "rsd_convnet_run"]
+GRAPH_SIZE_EXPORTS = ["rsd_convnet_scratch_bytes"]
 
 FMT_R32F, FMT_RG32F, FMT_RGBA32F, FMT_R16U, FMT_R8U, FMT_R8UNORM, FMT_R32U, FMT_UNKNOWN = range(8)
 FMT_R16F, FMT_RG16F, FMT_RGBA16F, FMT_RG8UNORM = 8, 9, 10, 11
@@ -477,6 +509,18 @@ def lib():
         L.rsd_image_equation_run.argtypes = [vp, C.POINTER(Texture), C.POINTER(Texture), vp]
         L.rsd_image_equation_release.restype = None
         L.rsd_image_equation_release.argtypes = [vp]
+        L.rsd_convnet_create.restype = st
+        L.rsd_convnet_create.argtypes = [C.POINTER(ConvNetLayer), u32, u32, C.POINTER(vp)]
+        L.rsd_convnet_load_dir.restype = st
+        L.rsd_convnet_load_dir.argtypes = [C.c_char_p, u32, C.POINTER(vp)]
+        L.rsd_convnet_release.restype = None
+        L.rsd_convnet_release.argtypes = [vp]
+        L.rsd_convnet_get_info.restype = st
+        L.rsd_convnet_get_info.argtypes = [vp, C.POINTER(ConvNetInfo)]
+        L.rsd_convnet_scratch_bytes.restype = C.c_uint64
+        L.rsd_convnet_scratch_bytes.argtypes = [vp, C.POINTER(ConvNetParams)]
+        L.rsd_convnet_run.restype = st
+        L.rsd_convnet_run.argtypes = [vp, C.POINTER(ConvNetParams), vp, vp, vp, vp, vp, vp, vp]
         L.rsd_graph_destroy.restype = None
         L.rsd_graph_destroy.argtypes = [vp]
         _lib = L

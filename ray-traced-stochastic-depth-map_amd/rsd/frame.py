@@ -485,6 +485,32 @@ class Renderer:
         abi.check(L.rsd_interleave(_ptr(out_layers), W, H, 1, _ptr(out), self.stream), "rsd_interleave")
         return out
 
+    def convnet(self, net, ao2=None, importance=None, depth=None, guard_band=None, **params):
+        """The dual AO map resolved by a learned net (rsd_convnet_run, the reference's ConvolutionalNet pass between
+        its DeinterleaveTexture and InterleaveTexture neighbours): net -- an rsd.convnet.ConvNet of 16 slices; ao2 --
+        default self.ao, a frame-size uint8 tensor x 2 of (bright, dark); importance -- a frame-size uint8 tensor,
+        needed when the net reads a third channel; depth -- a frame-size float32 tensor for the fourth channel,
+        default self.depth, the renderer's linear depth (scripts/SAVO_record.py feeds it divided by 1000).  params:
+        abi.ConvNetParams members (precision, clamp_output, numerics).  Returns a float32 tensor of the frame size;
+        texels outside the guard-band scissor read 0."""
+        t, L, W, H = self.torch, abi.lib(), self.cfg.fb_w, self.cfg.fb_h
+        ao2 = self.ao if ao2 is None else ao2
+        if ao2 is None or ao2.dim() != 3 or ao2.shape[2] != 2:
+            raise ValueError("ao2 must be a uint8 tensor of the frame size x 2 for (bright, dark)")
+        bright = self._frame_layers(ao2[..., 0], "ao2", t.uint8)
+        dark = self._frame_layers(ao2[..., 1], "ao2", t.uint8)
+        imp = self._frame_layers(importance, "importance", t.uint8) if net.channels_in[0] > 2 or importance is not None else None
+        z = self._frame_layers(self.depth if depth is None else depth, "depth", t.float32) if net.channels_in[0] > 3 else None
+        prm = abi.ConvNetParams(W, H, 16, self.cfg.guard_band if guard_band is None else guard_band,
+                                in_texel_bytes=(1, 1, 1, 4), **params)
+        scratch = t.empty(max(net.scratch_bytes(prm), 1), dtype=t.uint8, device=bright.device)
+        out_layers = t.zeros(tuple(bright.shape), dtype=t.float32, device=bright.device)
+        abi.check(L.rsd_convnet_run(net.h, C.byref(prm), _ptr(bright), _ptr(dark), _ptr(imp), _ptr(z), _ptr(scratch),
+                                    _ptr(out_layers), self.stream), "rsd_convnet_run")
+        out = t.empty((H, W), dtype=t.float32, device=bright.device)
+        abi.check(L.rsd_interleave(_ptr(out_layers), W, H, 4, _ptr(out), self.stream), "rsd_interleave")
+        return out
+
     def clear_intervals(self):
         abi.check(abi.lib().rsd_svao_clear_intervals(_ptr(self.ray_min), _ptr(self.ray_max), self.sd_w * self.sd_h,
                                                      self.stream), "rsd_svao_clear_intervals")
