@@ -1,12 +1,13 @@
 """Shared test helpers: struct conversion between librsd and the oracle, the oracle side of a whole
 frame (G-buffer -> pass 1 -> SD trace -> pass 2), the SVAO parameter sweep of test_svao_params.py /
-test_gpu_svao_params.py, and the grading of a fast-numerics frame against the exact oracle
-(test_gpu_numerics.py, test_gpu_svao_params.py)."""
+test_gpu_svao_params.py, the frames of odd geometry of test_odd_geometry.py / test_gpu_odd_geometry.py, and the
+grading of a fast-numerics frame against the exact oracle (test_gpu_numerics.py, test_gpu_svao_params.py)."""
 from __future__ import annotations
 
 import ctypes as C
 import json
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -105,6 +106,67 @@ def radius_in_pixels(cam, vao, depth):
         pa = rf / (f(cam.frameWidth) * z) * f(vao.resolution[0])
         pb = rf / (f(cam.frameHeight) * z) * f(vao.resolution[1])
         return pa + f(0.5) * (pb - pa)
+
+
+# ---- frames of odd geometry (test_odd_geometry.py checks on the oracle alone that each of them reaches the
+# branches it is meant to reach; test_gpu_odd_geometry.py runs the kernels on them)
+
+class OddFrame(NamedTuple):
+    name: str
+    visible_w: int
+    visible_h: int
+    guard: int
+    divisor: int
+    sd_guard_px: int
+    radius: float
+
+
+# arcade_tiny with its own camera, N = 4, max_count 8
+ODD_FRAMES = [
+    # odd prime width, odd guard band, divisor 3, sdGuard = 7 / 3 = 2, SD map 60 x 39
+    OddFrame("odd_div3", 157, 93, 5, 3, 7, 1.0),
+    # ceil(fb / 4): 111 x 75 -> 28 x 19, sdGuard 3, SD map 34 x 25
+    OddFrame("odd_div4", 97, 61, 7, 4, 13, 2.0),
+    # no guard band and sdGuard 0 (the generic pass 1), SD map 66 x 34
+    OddFrame("no_guards", 131, 67, 0, 2, 0, 2.0),
+    # smaller than one 32 x 32 pass-1 workgroup and than one 64-lane wave row; SD map 17 x 13
+    OddFrame("tiny", 20, 12, 3, 2, 5, 2.0),
+    # one pixel above a multiple of 32 in both axes (the last 32-row group holds one visible row), a one-pixel guard
+    # band, full-resolution SD map 105 x 73.  (65 x 33 with radius 4 stencils 1009 visible pixels, too close to the
+    # 1000 that test_odd_geometry.py asks for; this one 2879.)
+    OddFrame("one_over", 97, 65, 1, 1, 3, 3.0),
+]
+# the SD map sizes the shapes are meant to have: lowResolution = ceil(fb / divisor), sdGuard = sd_guard_px // divisor
+ODD_SD_SIZES = {"odd_div3": (60, 39), "odd_div4": (34, 25), "no_guards": (66, 34), "tiny": (17, 13),
+                "one_over": (105, 73)}
+
+
+def odd_second_pose(scene):
+    """A second camera pose of the scene (pos, target, up), far enough from its own for other SD texels to be
+    touched: the clean-tile tests' second frame."""
+    c = scene.camera
+    return ([c["pos"][0] + 1.5, c["pos"][1] + 0.25, c["pos"][2] - 2.0],
+            [c["target"][0] - 2.0, c["target"][1], c["target"][2]], list(c["up"]))
+
+
+def odd_frame(name):
+    return next(f for f in ODD_FRAMES if f.name == name)
+
+
+def odd_frame_config(f, N=4, max_count=8, **kw):
+    from rsd.frame import FrameConfig
+    return FrameConfig(visible_w=f.visible_w, visible_h=f.visible_h, guard_band=f.guard, divisor=f.divisor,
+                       sd_samples=N, max_count=max_count, sd_guard_px=f.sd_guard_px, radius=f.radius, **kw)
+
+
+def right_bottom_guard(cfg):
+    """A boolean image of the frame: the pixels of the right and bottom guard band, which pass 1's padded
+    dispatch (roundup32 of the visible size from the first visible pixel) reaches and the left / top band not."""
+    m = np.zeros((cfg.fb_h, cfg.fb_w), bool)
+    if cfg.guard_band:
+        m[cfg.fb_h - cfg.guard_band:, :] = True
+        m[:, cfg.fb_w - cfg.guard_band:] = True
+    return m
 
 
 # ---- fast numerics graded against the exact oracle (BASELINE.md section 4)
