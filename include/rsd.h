@@ -295,6 +295,46 @@ rsd_status rsd_bvh_build(const rsd_scene_desc* desc, void* dst, uint64_t capacit
                          uint32_t* tri_offset);
 void rsd_scene_release(rsd_scene* scene);
 
+/* --- dynamic scenes: move vertices, refit the BVH on the GPU (DESIGN.md 4 "Dynamic scenes") ----
+ * rsd_scene_upload_dynamic is rsd_scene_upload_alpha (alpha may be NULL) that also keeps on the device what a
+ * refit needs: the index buffer, a copy of the positions and, per wide node, its parent, its count of inner
+ * children, an arrival counter and a tight box (one extra allocation, rsd_scene_dynamic_info.dynamic_bytes).
+ * The tree is built without spatial splits, whose clipped boxes a refit cannot reproduce
+ * (RSD_ERR_UNSUPPORTED if it has any).  Scenes of the other upload calls are unchanged and refuse updates. */
+rsd_status rsd_scene_upload_dynamic(rsd_device* dev, const rsd_scene_desc* desc, const rsd_alpha_desc* alpha,
+                                    rsd_scene** out);
+/* New vertex positions, float3[vertex_count] (vertex_count = the upload's), from device memory
+ * (positions_on_device != 0) or from host memory, which is copied asynchronously on `stream` and must stay
+ * alive until that copy has run.  Stream-ordered, no host wait, no allocation: the copy, one launch that
+ * rewrites the triangle records' positions and one that refits every box of the tree (topology, primitive
+ * ids and flags stay: the bytes are rsd_bvh_refit's).  Every librsd entry issued afterwards on the same
+ * stream sees the moved geometry; ordering against work on other streams is the caller's.  The update marks
+ * the segment entry grid stale: traces walk from the root (same bits, slower) until
+ * rsd_scene_rebuild_entry_grid.  RSD_ERR_INVALID_ARG on a scene that is not dynamic. */
+rsd_status rsd_scene_update_positions(rsd_scene* scene, const float* positions, uint32_t vertex_count,
+                                      uint32_t positions_on_device, rsd_stream stream);
+/* The same for `count` vertices: d_positions[i] (float3) becomes the position of vertex d_vertex_ids[i]
+ * (both in device memory; an id >= vertex_count moves nothing; a vertex named twice takes either position).
+ * The refit still covers the whole tree. */
+rsd_status rsd_scene_update_subset(rsd_scene* scene, const uint32_t* d_vertex_ids, const float* d_positions,
+                                   uint32_t count, rsd_stream stream);
+/* Rebuild the segment entry grid from the scene's current boxes.  Synchronous: waits for the device, reads
+ * the nodes back, builds on host threads and swaps the device table in. */
+rsd_status rsd_scene_rebuild_entry_grid(rsd_scene* scene);
+typedef struct {
+    uint32_t dynamic;             /* 1: uploaded with rsd_scene_upload_dynamic */
+    uint32_t entry_grid_current;  /* 0: an update moved geometry since the entry grid was built (traces drop it) */
+    uint64_t updates;             /* rsd_scene_update_* calls applied */
+    uint64_t dynamic_bytes;       /* device bytes a dynamic scene holds beyond a static one */
+} rsd_scene_dynamic_info;
+rsd_status rsd_scene_dynamic_info_get(const rsd_scene* scene, rsd_scene_dynamic_info* out);
+/* The refit on the host, without a GPU: `bvh` (bvh_bytes, tri_offset: of rsd_bvh_build or
+ * rsd_scene_export_bvh) with the records' positions and every box rewritten for `positions`, into dst
+ * (bvh_bytes; may be bvh itself).  indices / triangle_count: the scene's.  The byte-exact statement of what
+ * an update leaves on the device.  RSD_ERR_UNSUPPORTED for a tree with spatial splits. */
+rsd_status rsd_bvh_refit(const void* bvh, uint64_t bvh_bytes, uint32_t tri_offset, const uint32_t* indices,
+                         uint32_t triangle_count, const float* positions, uint32_t vertex_count, void* dst);
+
 /* --- host helpers (no GPU work) ---------------------------------------------------- */
 /* RAY_CONE_SPREAD of the SD pass (StochasticDepthMapRT.cpp:266-267): Camera::
  * computeScreenSpacePixelSpreadAngle(height) (Camera.cpp:296-301) with the fovY of the 24 mm

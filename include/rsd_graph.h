@@ -52,6 +52,12 @@ rsd_status rsd_graph_add_edge(rsd_graph* g, const char* src, const char* dst);
 rsd_status rsd_graph_mark_output(rsd_graph* g, const char* name);
 /* scene + camera of the frame; call again with a new camera each frame (the camera is copied) */
 rsd_status rsd_graph_set_scene(rsd_graph* g, rsd_scene* scene, const rsd_camera* cam);
+/* Moved geometry (rsd.h rsd_scene_update_positions) for the graph's scene, which the application uploaded with
+ * rsd_scene_upload_dynamic before rsd_graph_set_scene: enqueued on `stream`, so the next rsd_graph_execute on
+ * that stream renders the moved scene.  Passes that keep history (TemporalAO, TemporalDepthPeel, the G-buffer's
+ * motion vectors) know the camera's motion only, not the geometry's. */
+rsd_status rsd_graph_update_scene_positions(rsd_graph* g, const float* positions, uint32_t vertex_count,
+                                            uint32_t positions_on_device, rsd_stream stream);
 /* external input bound to "pass.field" (caller-owned device memory) */
 rsd_status rsd_graph_set_input(rsd_graph* g, const char* name, const rsd_texture* tex);
 rsd_status rsd_graph_compile(rsd_graph* g, uint32_t width, uint32_t height, rsd_stream stream);

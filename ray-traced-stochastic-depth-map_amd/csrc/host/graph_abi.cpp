@@ -109,6 +109,17 @@ rsd_status rsd_graph_set_scene(rsd_graph* g, rsd_scene* scene, const rsd_camera*
     });
 }
 
+rsd_status rsd_graph_update_scene_positions(rsd_graph* g, const float* positions, uint32_t vertex_count,
+                                            uint32_t positions_on_device, rsd_stream stream) {
+    if (!g) return nullArg("rsd_graph_update_scene_positions");
+    if (!g->hasScene || !g->scene.scene) {
+        rsd::set_error("rsd_graph_update_scene_positions: no scene set");
+        return RSD_ERR_INVALID_ARG;
+    }
+    // passes hold the scene by handle and read its device tree every execute: nothing of theirs to refresh
+    return rsd_scene_update_positions(g->scene.scene, positions, vertex_count, positions_on_device, stream);
+}
+
 rsd_status rsd_graph_set_input(rsd_graph* g, const char* name, const rsd_texture* tex) {
     if (!g || !name || !tex || !tex->ptr) return nullArg("rsd_graph_set_input");
     return guarded("rsd_graph_set_input", [&] {

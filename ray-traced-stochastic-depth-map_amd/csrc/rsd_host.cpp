@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 
+#include "bvh_refit.h"
 #include "entry_grid.h"
 #include "rsd_internal.h"
 
@@ -90,7 +91,90 @@ unsigned build_threads() {
 }
 }  // namespace
 
+namespace {
+// the segment entry grid of `nodes` (the scene's wide nodes on the host) into a fresh device table, replacing
+// the scene's (RSD_ENTRY_CELLS bounds its cells, 0 = none)
+rsd_status upload_entry_grid(rsd_scene* s, const std::vector<float>& nodes, unsigned threads, const char* who) {
+    uint64_t maxCells = 1ull << 21;
+    if (const char* env = std::getenv("RSD_ENTRY_CELLS")) maxCells = (uint64_t)std::atoll(env);
+    rsd::EntryGrid g;
+    if (s->triangle_count && maxCells) g = rsd::build_entry_grid(nodes, s->tri_offset, maxCells, threads);
+    void* d = nullptr;
+    const size_t sb = g.slots.size() * 4, ib = g.items.size() * 4;
+    if (g.cells) {
+        hipError_t e = hipMalloc(&d, sb + ib);
+        if (e == hipSuccess) e = hipMemcpy(d, g.slots.data(), sb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(static_cast<char*>(d) + sb, g.items.data(), ib, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return rsd::hip_fail(e, who);
+        }
+    }
+    if (s->d_entry) {
+        (void)hipFree(s->d_entry);
+        s->device_bytes -= s->entry_bytes;
+    }
+    s->d_entry = d;
+    s->entry_bytes = g.cells ? sb + ib : 0;
+    s->entry_items_off = g.cells ? sb : 0;
+    uint32_t bits = 0;
+    while (g.cells && (4ull << bits) < g.slots.size()) ++bits;
+    s->entry_bits = bits;
+    s->entry_probe = g.cells ? g.max_probe : 0;
+    s->entry_rmax = g.cells ? g.rmax : 0;
+    s->entry_cells = g.cells;
+    for (int k = 0; k < 3; ++k) s->entry_origin[k] = g.cells ? g.origin[k] : 0.0f;
+    s->entry_extent = g.cells ? g.extent : 0.0f;
+    s->entry_build_ms = g.cells ? g.build_ms : 0.0;
+    s->device_bytes += s->entry_bytes;
+    return RSD_OK;
+}
+
+// What a refit needs, in one allocation (rsd_internal.h DynamicData): the index buffer, the positions, and per
+// wide node its parent, its count of inner children, a zeroed arrival counter and a tight box.
+rsd_status upload_dynamic_data(rsd_scene* s, const rsd_scene_desc* desc, const rsd::FlatBvh& bvh) {
+    const uint32_t nn = s->node_count, nt = desc->triangle_count, nv = desc->vertex_count;
+    std::vector<uint32_t> parent(nn), inner(nn);
+    if (!rsd::refit_topology(reinterpret_cast<const uint32_t*>(bvh.nodes.data()), nn, nt, parent.data(), inner.data())) {
+        set_error("rsd_scene_upload_dynamic: the built tree is not one a refit can walk");
+        return RSD_ERR_UNSUPPORTED;
+    }
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t oInd = 0, oPos = al(12 * (size_t)nt), oPar = oPos + al(12 * (size_t)nv), oInner = oPar + al(4 * (size_t)nn),
+                 oArr = oInner + al(4 * (size_t)nn), oTight = oArr + al(4 * (size_t)nn),
+                 total = oTight + al(24 * (size_t)nn);
+    char* d = nullptr;
+    hipError_t e = hipMalloc(&d, total);
+    if (e == hipSuccess) e = hipMemset(d, 0, total);
+    if (e == hipSuccess && nt) e = hipMemcpy(d + oInd, desc->indices, 12 * (size_t)nt, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nv) e = hipMemcpy(d + oPos, desc->positions, 12 * (size_t)nv, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nn) e = hipMemcpy(d + oPar, parent.data(), 4 * (size_t)nn, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nn) e = hipMemcpy(d + oInner, inner.data(), 4 * (size_t)nn, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return rsd::hip_fail(e, "rsd_scene_upload_dynamic");
+    }
+    s->d_dyn = d;
+    s->dyn.indices = reinterpret_cast<uint32_t*>(d + oInd);
+    s->dyn.positions = reinterpret_cast<float*>(d + oPos);
+    s->dyn.parent = reinterpret_cast<uint32_t*>(d + oPar);
+    s->dyn.inner = reinterpret_cast<uint32_t*>(d + oInner);
+    s->dyn.arrive = reinterpret_cast<uint32_t*>(d + oArr);
+    s->dyn.tight = reinterpret_cast<uint32_t*>(d + oTight);
+    s->dyn_bytes = total;
+    s->device_bytes += total;
+    return RSD_OK;
+}
+
+rsd_status scene_upload(rsd_device* dev, const rsd_scene_desc* desc, rsd_scene** out, bool dynamic);
+}  // namespace
+
 extern "C" rsd_status rsd_scene_upload(rsd_device* dev, const rsd_scene_desc* desc, rsd_scene** out) {
+    return scene_upload(dev, desc, out, false);
+}
+
+namespace {
+rsd_status scene_upload(rsd_device* dev, const rsd_scene_desc* desc, rsd_scene** out, bool dynamic) {
     if (!dev || !desc || !out || (desc->triangle_count && (!desc->positions || !desc->indices))) {
         set_error("rsd_scene_upload: null argument");
         return RSD_ERR_INVALID_ARG;
@@ -107,11 +191,18 @@ extern "C" rsd_status rsd_scene_upload(rsd_device* dev, const rsd_scene_desc* de
     }
     RSD_HIP(hipSetDevice(dev->hip_device));
     const unsigned threads = build_threads();
+    rsd::BvhOptions opt;
+    opt.split_budget = 0.0;  // a refit cannot reproduce the clipped boxes of spatial-split references
     rsd::FlatBvh bvh = rsd::build_bvh(desc->positions, desc->vertex_count, desc->indices, desc->triangle_count,
-                                      desc->triangle_flags, threads);
+                                      desc->triangle_flags, threads, opt);
+    if (dynamic && (bvh.stats.spatial_splits != 0 || bvh.stats.references != desc->triangle_count)) {
+        set_error("rsd_scene_upload_dynamic: the tree has spatial splits, which a refit cannot keep");
+        return RSD_ERR_UNSUPPORTED;
+    }
     auto* s = new rsd_scene;
     s->dev = dev;
     s->triangle_count = desc->triangle_count;
+    s->vertex_count = desc->vertex_count;
     s->node_count = (uint32_t)(bvh.nodes.size() / 32);
     s->stats = bvh.stats;
     s->build_threads = threads;
@@ -154,42 +245,17 @@ extern "C" rsd_status rsd_scene_upload(rsd_device* dev, const rsd_scene_desc* de
         }
         s->device_bytes += pr.size() * 4;
     }
-    // segment entry grid (RSD_ENTRY_CELLS bounds its cells, 0 = none)
-    uint64_t maxCells = 1ull << 21;
-    if (const char* env = std::getenv("RSD_ENTRY_CELLS")) maxCells = (uint64_t)std::atoll(env);
-    if (desc->triangle_count && maxCells) {
-        const rsd::EntryGrid g = rsd::build_entry_grid(bvh.nodes, s->tri_offset, maxCells, threads);
-        if (g.cells) {
-            const size_t sb = g.slots.size() * 4, ib = g.items.size() * 4;
-            void* d = nullptr;
-            e = hipMalloc(&d, sb + ib);
-            if (e == hipSuccess) e = hipMemcpy(d, g.slots.data(), sb, hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(static_cast<char*>(d) + sb, g.items.data(), ib, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                rsd_status st = rsd::hip_fail(e, "rsd_scene_upload (entry grid)");
-                (void)hipFree(d);
-                (void)hipFree(s->d_prim_rec);
-                (void)hipFree(s->d_nodes);
-                delete s;
-                return st;
-            }
-            s->d_entry = d;
-            s->entry_items_off = sb;
-            uint32_t bits = 0;
-            while ((4ull << bits) < g.slots.size()) ++bits;
-            s->entry_bits = bits;
-            s->entry_probe = g.max_probe;
-            s->entry_rmax = g.rmax;
-            s->entry_cells = g.cells;
-            for (int k = 0; k < 3; ++k) s->entry_origin[k] = g.origin[k];
-            s->entry_extent = g.extent;
-            s->entry_build_ms = g.build_ms;
-            s->device_bytes += sb + ib;
-        }
+    // segment entry grid
+    rsd_status st = upload_entry_grid(s, bvh.nodes, threads, "rsd_scene_upload (entry grid)");
+    if (st == RSD_OK && dynamic) st = upload_dynamic_data(s, desc, bvh);
+    if (st != RSD_OK) {
+        rsd_scene_release(s);
+        return st;
     }
     *out = s;
     return RSD_OK;
 }
+}  // namespace
 
 namespace {
 // MaterialHeader stores the alpha threshold as float16 (MaterialData.slang:99): round to
@@ -232,9 +298,10 @@ void build_mips(const rsd_alpha_texture& t, std::vector<uint8_t>& out, uint32_t&
 }
 }  // namespace
 
-extern "C" rsd_status rsd_scene_upload_alpha(rsd_device* dev, const rsd_scene_desc* desc, const rsd_alpha_desc* alpha,
-                                             rsd_scene** out) {
-    if (!alpha) return rsd_scene_upload(dev, desc, out);
+namespace {
+rsd_status scene_upload_alpha(rsd_device* dev, const rsd_scene_desc* desc, const rsd_alpha_desc* alpha, rsd_scene** out,
+                              bool dynamic) {
+    if (!alpha) return scene_upload(dev, desc, out, dynamic);
     if (!dev || !desc || !out || !alpha->triangle_material || !alpha->materials || alpha->material_count == 0 ||
         (desc->vertex_count && !alpha->texcoords) || (alpha->texture_count && !alpha->textures)) {
         set_error("rsd_scene_upload_alpha: null argument");
@@ -259,7 +326,7 @@ extern "C" rsd_status rsd_scene_upload_alpha(rsd_device* dev, const rsd_scene_de
             set_error("rsd_scene_upload_alpha: triangle_material out of range of material_count");
             return RSD_ERR_INVALID_ARG;
         }
-    rsd_status st = rsd_scene_upload(dev, desc, out);
+    rsd_status st = scene_upload(dev, desc, out, dynamic);
     if (st != RSD_OK) return st;
     rsd_scene* s = *out;
     const uint32_t nt = desc->triangle_count, nm = alpha->material_count, nx = alpha->texture_count;
@@ -320,6 +387,17 @@ extern "C" rsd_status rsd_scene_upload_alpha(rsd_device* dev, const rsd_scene_de
     s->device_bytes += total;
     return RSD_OK;
 }
+}  // namespace
+
+extern "C" rsd_status rsd_scene_upload_alpha(rsd_device* dev, const rsd_scene_desc* desc, const rsd_alpha_desc* alpha,
+                                             rsd_scene** out) {
+    return scene_upload_alpha(dev, desc, alpha, out, false);
+}
+
+extern "C" rsd_status rsd_scene_upload_dynamic(rsd_device* dev, const rsd_scene_desc* desc, const rsd_alpha_desc* alpha,
+                                               rsd_scene** out) {
+    return scene_upload_alpha(dev, desc, alpha, out, true);
+}
 
 extern "C" float rsd_ray_cone_spread(float focal_length, uint32_t height) {
     // every SD trace asks for it with the frame's (focal length, height): keep the last answer per thread
@@ -352,6 +430,133 @@ extern "C" rsd_status rsd_scene_info_get(const rsd_scene* s, rsd_scene_info* out
     out->device_bytes = s->device_bytes;
     out->build_threads = s->build_threads;
     out->entry_cells = s->entry_cells;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_scene_dynamic_info_get(const rsd_scene* s, rsd_scene_dynamic_info* out) {
+    if (!s || !out) {
+        set_error("rsd_scene_dynamic_info_get: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    out->dynamic = s->d_dyn ? 1u : 0u;
+    out->entry_grid_current = s->entry_stale ? 0u : 1u;
+    out->updates = s->updates;
+    out->dynamic_bytes = s->dyn_bytes;
+    return RSD_OK;
+}
+
+namespace {
+rsd_status require_dynamic(const rsd_scene* s, const char* who) {
+    if (!s) {
+        set_error(std::string(who) + ": null scene");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (!s->d_dyn) {
+        set_error(std::string(who) + ": the scene is not dynamic (upload it with rsd_scene_upload_dynamic)");
+        return RSD_ERR_INVALID_ARG;
+    }
+    return RSD_OK;
+}
+}  // namespace
+
+extern "C" rsd_status rsd_scene_update_positions(rsd_scene* s, const float* positions, uint32_t vertex_count,
+                                                 uint32_t positions_on_device, rsd_stream stream) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_update_positions"); st != RSD_OK) return st;
+    if (vertex_count != s->vertex_count) {
+        set_error("rsd_scene_update_positions: vertex_count " + std::to_string(vertex_count) + " is not the upload's " +
+                  std::to_string(s->vertex_count));
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (!positions && vertex_count) {
+        set_error("rsd_scene_update_positions: null positions");
+        return RSD_ERR_INVALID_ARG;
+    }
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    hipStream_t hs = (hipStream_t)stream;
+    if (vertex_count)
+        RSD_HIP(hipMemcpyAsync(s->dyn.positions, positions, 12 * (size_t)vertex_count,
+                               positions_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, hs));
+    s->entry_stale = s->entry_stale || s->d_entry != nullptr;
+    ++s->updates;
+    return rsd::refit_enqueue(s, hs);
+}
+
+extern "C" rsd_status rsd_scene_update_subset(rsd_scene* s, const uint32_t* d_vertex_ids, const float* d_positions,
+                                              uint32_t count, rsd_stream stream) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_update_subset"); st != RSD_OK) return st;
+    if (count && (!d_vertex_ids || !d_positions)) {
+        set_error("rsd_scene_update_subset: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    hipStream_t hs = (hipStream_t)stream;
+    if (rsd_status st = rsd::refit_scatter_enqueue(s, d_vertex_ids, d_positions, count, hs); st != RSD_OK) return st;
+    s->entry_stale = s->entry_stale || s->d_entry != nullptr;
+    ++s->updates;
+    return rsd::refit_enqueue(s, hs);
+}
+
+extern "C" rsd_status rsd_scene_rebuild_entry_grid(rsd_scene* s) {
+    if (!s) {
+        set_error("rsd_scene_rebuild_entry_grid: null scene");
+        return RSD_ERR_INVALID_ARG;
+    }
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    // synchronous: every update and every trace enqueued so far has finished before the nodes are read
+    // back and before the table those traces read is freed
+    RSD_HIP(hipDeviceSynchronize());
+    std::vector<float> nodes(4 * (size_t)s->tri_offset);
+    if (!nodes.empty()) RSD_HIP(hipMemcpy(nodes.data(), s->d_nodes, nodes.size() * 4, hipMemcpyDeviceToHost));
+    rsd_status st = upload_entry_grid(s, nodes, s->build_threads ? s->build_threads : build_threads(),
+                                      "rsd_scene_rebuild_entry_grid");
+    if (st != RSD_OK) return st;
+    s->entry_stale = false;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_bvh_refit(const void* bvh, uint64_t bvh_bytes, uint32_t tri_offset, const uint32_t* indices,
+                                    uint32_t triangle_count, const float* positions, uint32_t vertex_count, void* dst) {
+    const uint32_t nt = triangle_count;
+    if (!bvh || !dst || (nt && (!indices || !positions))) {
+        set_error("rsd_bvh_refit: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    const uint64_t nodeBytes = 16ull * tri_offset;
+    if (tri_offset % 8 != 0 || bvh_bytes < nodeBytes + 12 * 16 || (bvh_bytes - nodeBytes - 12 * 16) % 48 != 0) {
+        set_error("rsd_bvh_refit: bvh_bytes / tri_offset are not those of rsd_bvh_build");
+        return RSD_ERR_INVALID_ARG;
+    }
+    const uint64_t records = (bvh_bytes - nodeBytes - 12 * 16) / 48;
+    const uint32_t nn = tri_offset / 8;
+    const uint32_t* src = static_cast<const uint32_t*>(bvh);
+    // a triangle with several records (spatial splits) carries clipped boxes a refit cannot reproduce
+    std::vector<uint8_t> seen(nt, 0);
+    bool split = records != nt;
+    for (uint64_t r = 0; r < records && !split; ++r) {
+        const uint32_t prim = src[4 * (size_t)tri_offset + 12 * r + 3];
+        if (prim >= nt) {
+            set_error("rsd_bvh_refit: a record's primitive id is out of range of triangle_count");
+            return RSD_ERR_INVALID_ARG;
+        }
+        split = seen[prim] != 0;
+        seen[prim] = 1;
+    }
+    if (split) {
+        set_error("rsd_bvh_refit: the tree has spatial splits (several records of one triangle)");
+        return RSD_ERR_UNSUPPORTED;
+    }
+    for (uint64_t i = 0; i < 3ull * nt; ++i)
+        if (indices[i] >= vertex_count) {
+            set_error("rsd_bvh_refit: index out of range of vertex_count");
+            return RSD_ERR_INVALID_ARG;
+        }
+    std::vector<uint32_t> parent(nn), inner(nn);
+    if (!rsd::refit_topology(src, nn, nt, parent.data(), inner.data())) {
+        set_error("rsd_bvh_refit: not a tree of rsd_bvh_build");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (dst != bvh) std::memmove(dst, bvh, bvh_bytes);
+    rsd::refit_host(static_cast<uint32_t*>(dst), nn, indices, nt, positions);
     return RSD_OK;
 }
 
@@ -410,6 +615,7 @@ extern "C" void rsd_scene_release(rsd_scene* s) {
     (void)hipFree(s->d_alpha);
     (void)hipFree(s->d_entry);
     (void)hipFree(s->d_rtao_table);
+    (void)hipFree(s->d_dyn);
     delete s;
 }
 

@@ -62,6 +62,17 @@ struct SdWorkspace {
     size_t raster_cap = 0;         // bytes
 };
 void release_sd_workspaces(rsd_scene* s);
+
+// What a dynamic scene (rsd_scene_upload_dynamic) keeps on the device for a refit (csrc/bvh_refit.hip):
+// pointers into rsd_scene.d_dyn, one allocation
+struct DynamicData {
+    uint32_t* indices = nullptr;  // uint32[3 * triangle_count]
+    float* positions = nullptr;   // float3[vertex_count]: the scene's copy, what the records were last written from
+    uint32_t* parent = nullptr;   // per wide node: parent node << 2 | slot (the root: 0xffffffff)
+    uint32_t* inner = nullptr;    // per wide node: its count of inner children
+    uint32_t* arrive = nullptr;   // per wide node: inner children arrived in this refit (zero between refits)
+    uint32_t* tight = nullptr;    // per wide node: its tight box as keys, lo[3] hi[3] (bvh_refit.h)
+};
 }  // namespace rsd
 
 struct rsd_scene {
@@ -85,13 +96,29 @@ struct rsd_scene {
     uint32_t entry_bits = 0, entry_probe = 0, entry_rmax = 0, entry_cells = 0;
     float entry_origin[3] = {0.0f, 0.0f, 0.0f}, entry_extent = 0.0f;
     uint64_t entry_items_off = 0;  // bytes from d_entry to the item array
+    uint64_t entry_bytes = 0;      // the d_entry allocation
     double entry_build_ms = 0.0;
     uint32_t* d_rtao_table = nullptr;  // RTAO's sample table (rtao.hip), uploaded by the first rsd_rtao
+    // dynamic scenes (rsd_scene_upload_dynamic): d_dyn == null for every other scene
+    void* d_dyn = nullptr;
+    rsd::DynamicData dyn;
+    uint32_t vertex_count = 0;
+    uint64_t dyn_bytes = 0;
+    uint64_t updates = 0;        // rsd_scene_update_* calls enqueued so far
+    // an update moved geometry since the entry grid was built: traces pass no table (the root-start path)
+    // until rsd_scene_rebuild_entry_grid
+    bool entry_stale = false;
 };
 
 namespace rsd {
 void set_error(const std::string& msg);
 rsd_status hip_fail(hipError_t e, const char* what);
+
+// bvh_refit.hip: the launches of one update of a dynamic scene on `st` -- scatter `count` positions into the
+// scene's copy; rewrite the records from that copy and refit every box
+rsd_status refit_scatter_enqueue(rsd_scene* s, const uint32_t* d_ids, const float* d_positions, uint32_t count,
+                                 hipStream_t st);
+rsd_status refit_enqueue(rsd_scene* s, hipStream_t st);
 
 // sd_trace.hip: the stratified coverage-mask tables of N samples on HIP device `dev` (indices [N + 1], look-up
 // table [2^N]), uploaded once per (device, N) and never freed; shared by the SD trace and sd_raster.hip

@@ -2659,10 +2659,12 @@ rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_p
     a.tileCount = ((sd_w + kTile - 1) / kTile) * ((sd_h + kTile - 1) / kTile);
     a.primRec = scene->d_prim_rec;
     a.entOn = 0u;
-    a.entSlots = static_cast<const uint4*>(scene->d_entry);
-    a.entItems = scene->d_entry ? reinterpret_cast<const float4*>(static_cast<const char*>(scene->d_entry) +
-                                                                   scene->entry_items_off)
-                                : nullptr;
+    // a dynamic scene whose geometry moved since the grid was built passes no table: its cells' frontiers need
+    // not cover the triangles that moved into them (rsd_scene_rebuild_entry_grid makes it current again)
+    const void* const entry = scene->entry_stale ? nullptr : scene->d_entry;
+    a.entSlots = static_cast<const uint4*>(entry);
+    a.entItems = entry ? reinterpret_cast<const float4*>(static_cast<const char*>(entry) + scene->entry_items_off)
+                       : nullptr;
     a.entBits = scene->entry_bits;
     a.entProbe = scene->entry_probe;
     a.entRmax = (int)scene->entry_rmax;
@@ -2731,7 +2733,7 @@ rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_p
     // split walk (trace -> keys -> resolve) when one chunk of K keys decides every texel
     const bool split = p->implementation != RSD_SD_COVERAGE_MASK && p->max_count <= K;
     const size_t queueBytes = need_q * 32, keyBytes = split ? need_q * K * sizeof(uint2) : 0;
-    const size_t entBytes = scene->d_entry ? need_q * kEntryCap * sizeof(uint32_t) : 0;
+    const size_t entBytes = entry ? need_q * kEntryCap * sizeof(uint32_t) : 0;
     const size_t touchBytes = (size_t)touchCap * kQueueParts * sizeof(uint32_t);
     if (ws->queue_cap < queueBytes + keyBytes + entBytes + touchBytes) {
         RSD_HIP(hipStreamSynchronize(s));

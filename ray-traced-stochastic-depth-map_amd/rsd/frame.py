@@ -200,12 +200,34 @@ def host_bvh(scene: Scene):
     return buf, off.value
 
 
+def host_bvh_refit(bvh, tri_offset: int, indices, positions):
+    """rsd_bvh_refit: the BVH bytes `bvh` (float32 array of host_bvh() or GpuScene.export_bvh()) refitted to
+    `positions` on the host, as a new float32 array -- what an update of a dynamic scene leaves on the device."""
+    bvh = np.ascontiguousarray(bvh, np.float32)
+    ind = np.ascontiguousarray(indices, np.uint32)
+    pos = np.ascontiguousarray(positions, np.float32)
+    out = np.empty_like(bvh)
+    abi.check(abi.lib().rsd_bvh_refit(bvh.ctypes.data, bvh.nbytes, int(tri_offset), ind.ctypes.data, ind.size // 3,
+                                      pos.ctypes.data, pos.size // 3, out.ctypes.data), "rsd_bvh_refit")
+    return out
+
+
 class GpuScene:
-    def __init__(self, dev: Device, scene: Scene):
+    def __init__(self, dev: Device, scene: Scene, dynamic: bool = False):
+        """dynamic=True: rsd_scene_upload_dynamic -- the scene's vertices can move (update_positions,
+        update_subset), its BVH being refitted on the GPU."""
         desc = abi.SceneDesc(scene.positions.ctypes.data, scene.positions.shape[0], scene.indices.ctypes.data,
                              scene.indices.shape[0], scene.flags.ctypes.data)
         h = C.c_void_p()
-        if scene.alpha is None:
+        self.dev = dev
+        self.dynamic = bool(dynamic)
+        self.vertex_count = int(scene.positions.shape[0])
+        if dynamic:
+            ad, keep = alpha_desc(scene.alpha) if scene.alpha is not None else (None, None)
+            abi.check(abi.lib().rsd_scene_upload_dynamic(dev.h, C.byref(desc), C.byref(ad) if ad is not None else None,
+                                                         C.byref(h)), "rsd_scene_upload_dynamic")
+            del keep
+        elif scene.alpha is None:
             abi.check(abi.lib().rsd_scene_upload(dev.h, C.byref(desc), C.byref(h)), "rsd_scene_upload")
         else:
             ad, keep = alpha_desc(scene.alpha)
@@ -226,6 +248,57 @@ class GpuScene:
                   "rsd_scene_export_bvh")
         return buf, off.value
 
+    @staticmethod
+    def _stream(stream):
+        if stream is not None:
+            return stream
+        import torch
+        return torch.cuda.current_stream().cuda_stream
+
+    def update_positions(self, positions, stream=None):
+        """Move the scene (rsd_scene_update_positions): `positions` is a float32 [vertex_count, 3] numpy array
+        (copied from the host on the stream: it is kept alive here until the next update) or a contiguous
+        float32 torch tensor on the scene's device.  stream: a raw HIP stream, default torch's current one.
+        Stream-ordered; what is issued afterwards on that stream renders the moved geometry."""
+        if isinstance(positions, np.ndarray) or not hasattr(positions, "data_ptr"):
+            pos = np.ascontiguousarray(positions, np.float32)
+            ptr, n, on_device = pos.ctypes.data, pos.size // 3, 0
+        else:
+            pos = positions.contiguous()
+            if not pos.is_cuda or str(pos.dtype) != "torch.float32":
+                raise ValueError("update_positions: a tensor must be float32 and on the GPU")
+            ptr, n, on_device = pos.data_ptr(), pos.numel() // 3, 1
+        abi.check(abi.lib().rsd_scene_update_positions(self.h, ptr, n, on_device, self._stream(stream)),
+                  "rsd_scene_update_positions")
+        self._keep = pos
+
+    def update_subset(self, ids, positions, stream=None):
+        """Move some vertices (rsd_scene_update_subset): ids -- int32 / uint32 [count], positions -- float32
+        [count, 3]; numpy arrays are copied to the device first, torch tensors on the device are used as they
+        are."""
+        import torch
+        dv = torch.device("cuda", self.dev.index)
+        if not hasattr(ids, "data_ptr"):
+            ids = torch.from_numpy(np.ascontiguousarray(ids, np.uint32).view(np.int32)).to(dv)
+        if not hasattr(positions, "data_ptr"):
+            positions = torch.from_numpy(np.ascontiguousarray(positions, np.float32)).to(dv)
+        ids, positions = ids.contiguous(), positions.contiguous()
+        if ids.element_size() != 4 or str(positions.dtype) != "torch.float32" or positions.numel() != 3 * ids.numel():
+            raise ValueError("update_subset: ids must be 32-bit integers [count], positions float32 [count, 3]")
+        abi.check(abi.lib().rsd_scene_update_subset(self.h, ids.data_ptr(), positions.data_ptr(), ids.numel(),
+                                                    self._stream(stream)), "rsd_scene_update_subset")
+        self._keep = (ids, positions)
+
+    def rebuild_entry_grid(self):
+        """Make the segment entry grid current again after updates (rsd_scene_rebuild_entry_grid; synchronous)."""
+        abi.check(abi.lib().rsd_scene_rebuild_entry_grid(self.h), "rsd_scene_rebuild_entry_grid")
+        abi.check(abi.lib().rsd_scene_info_get(self.h, C.byref(self.info)), "rsd_scene_info_get")
+
+    def dynamic_info(self) -> abi.SceneDynamicInfo:
+        d = abi.SceneDynamicInfo()
+        abi.check(abi.lib().rsd_scene_dynamic_info_get(self.h, C.byref(d)), "rsd_scene_dynamic_info_get")
+        return d
+
     def release(self):
         if self.h:
             abi.lib().rsd_scene_release(self.h)
@@ -243,7 +316,8 @@ class Renderer:
     """Owns the frame buffers of one config on one GPU and runs the hot path."""
 
     def __init__(self, scene: Scene, cfg: FrameConfig, device: int = 0, gpu_scene: GpuScene | None = None,
-                 dev: Device | None = None):
+                 dev: Device | None = None, dynamic: bool = False):
+        """dynamic=True uploads the scene as a dynamic one (GpuScene(dynamic=True)): update_positions() moves it."""
         import torch
         global _raw_stream
         self.torch = torch
@@ -253,7 +327,7 @@ class Renderer:
         self.scene = scene
         self.dev = dev or Device(device)
         torch.cuda.set_device(self.dev.index)
-        self.gscene = gpu_scene or GpuScene(self.dev, scene)
+        self.gscene = gpu_scene or GpuScene(self.dev, scene, dynamic=dynamic)
         self.cam = make_camera(scene, cfg)
         self.vao, self.sd_w, self.sd_h = make_vao(cfg)
         self.sdp = sd_params(cfg, self.vao.sdGuard)
@@ -351,6 +425,14 @@ class Renderer:
         pose.  librsd copies the camera into every launch's arguments, so frames already
         enqueued keep the pose they were issued with."""
         self.cam = look_at(pos, target, up, self.cfg)
+
+    def update_positions(self, positions):
+        """Move the scene's vertices (GpuScene.update_positions on this renderer's stream) and keep
+        self.scene.positions in step, so that the oracle and the checkers see the moved scene.  The renderer's
+        Scene object is replaced by a copy with the new positions; the caller's stays as it was."""
+        self.gscene.update_positions(positions, stream=self.stream)
+        host = positions.detach().cpu().numpy() if hasattr(positions, "data_ptr") else positions
+        self.scene = dataclasses.replace(self.scene, positions=np.array(host, np.float32).reshape(-1, 3))
 
     @property
     def stream(self):

@@ -100,6 +100,22 @@ class RenderGraph:
     def set_scene(self, scene_handle, camera: abi.Camera):
         abi.check(self._L.rsd_graph_set_scene(self._h, scene_handle, C.byref(camera)), "set_scene")
 
+    def update_positions(self, positions, stream=None):
+        """Move the vertices of the graph's scene -- a dynamic one, GpuScene(dev, scene, dynamic=True), given to
+        set_scene -- on `stream` (rsd_graph_update_scene_positions): the next execute on that stream renders the
+        moved geometry.  positions: float32 [vertex_count, 3], a numpy array (kept alive here until the next
+        update) or a torch tensor on the device."""
+        import numpy as np
+        if hasattr(positions, "data_ptr"):
+            pos = positions.contiguous()
+            ptr, n, on_device = pos.data_ptr(), pos.numel() // 3, 1
+        else:
+            pos = np.ascontiguousarray(positions, np.float32)
+            ptr, n, on_device = pos.ctypes.data, pos.size // 3, 0
+        abi.check(self._L.rsd_graph_update_scene_positions(self._h, ptr, n, on_device, stream),
+                  "rsd_graph_update_scene_positions")
+        self._keep = [pos]
+
     def set_input(self, name: str, ptr: int, width: int, height: int, fmt: int, layers: int = 1):
         t = abi.Texture(C.c_void_p(ptr), width, height, layers, fmt, 0)
         abi.check(self._L.rsd_graph_set_input(self._h, name.encode(), C.byref(t)), f"set_input({name!r})")
