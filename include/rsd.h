@@ -515,7 +515,14 @@ rsd_status rsd_svao_pass2(const rsd_camera* cam, const rsd_vao_data* vao, const 
  * compute pass (SVAORaster2.ps.slang:9-65, SVAO.cpp:432-455; ray_pipeline = 0: visible pixels)
  * and the ray pipeline (Ray.rt.slang, SVAO.cpp:408-431; ray_pipeline = 1: the rayGen grid covers
  * the frame from the guard band to the right/bottom edge).  Pass 1 must have run with
- * secondary_depth_mode = 3.  cull_mode: SVAO's CULL_MODE_RAY_FLAG (rsd_cull_mode). */
+ * secondary_depth_mode = 3; a d_stencil texel that pass 1 did not write (left of or above the guard
+ * band, beyond its roundup32(visible) dispatch) must hold 0, the reference's cleared stencil
+ * (SVAO.cpp:307): the ray_pipeline = 1 grid reads those on the right and at the bottom.  A direction
+ * bit that pass 1 does not set for its pixel (a sample it rejects: sphereStart - sphereEnd at most a
+ * tenth of the sphere's height) makes the kernel trace with that sample's position, uv and
+ * isInScreen uninitialised (sample_init returns before it fills them, rt_dir does not test its
+ * result): pass 1's own stencil never holds such a bit, an arbitrary word may.
+ * cull_mode: SVAO's CULL_MODE_RAY_FLAG (rsd_cull_mode). */
 rsd_status rsd_svao_pass2_raytraced(rsd_scene* scene, const rsd_camera* cam, const rsd_vao_data* vao,
                                     const rsd_svao_params* params, const float* d_depth, const uint16_t* d_normals,
                                     uint32_t width, uint32_t height, const uint8_t* d_stencil, uint8_t* d_ao,

@@ -33,14 +33,15 @@ def build(oracle, out_dir):
 
 
 class Case:
-    """One small scene with its oracle scene and the camera of a W x H frame."""
+    """One small scene with its oracle scene and the camera of a frame of `size` (width, height), W x H by default."""
 
-    def __init__(self, oracle, kind):
+    def __init__(self, oracle, kind, size=(W, H)):
         from rsd.frame import FrameConfig, make_camera
         from rsd.scenes import make_scene
         name, tris = SCENES[kind]
         self.scene = make_scene(name, target_tris=tris)
-        self.cfg = FrameConfig(visible_w=W, visible_h=H, guard_band=0)
+        self.size = tuple(size)
+        self.cfg = FrameConfig(visible_w=size[0], visible_h=size[1], guard_band=0)
         self.cam = make_camera(self.scene, self.cfg)
         from helpers import to_oracle
         self.ocam = to_oracle(self.cam, oracle.Camera)

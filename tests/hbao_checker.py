@@ -156,13 +156,14 @@ def tie_case(width=64, height=48):
     return dict(cam=cam, layers=np.full_like(s["layers"], z), normal_w=s["normal_w"], rand=rand, radius=float(radius))
 
 
-def synthetic(width, height):
+def synthetic(width, height, zero_patch=16):
     """One synthetic frame: random linear depth in [2, 12] with smooth patches (two ramps and a stepped
     plateau, where the bright channel takes intermediate values), a patch at farZ, a patch of depth 0 in the
     top-left corner (the NaN taps: a texel there has P = 0 and an infinite radius in uv, whose lerp is NaN, so
     every tap's uv, S, VdotV and NdotV = 0 * inf or NaN are NaN and saturate turns them into no occlusion; 16
     pixels wide, so at guard band 8 half of it lies inside the scissor), random unit normals (about
-    half of them facing away from the camera) and a second layer 0.05 to 3 behind the first.
+    half of them facing away from the camera) and a second layer 0.05 to 3 behind the first.  zero_patch: the side
+    of the depth-0 patch, for frames that 16 x 16 pixels would cover.
     Returns dict(cam, z, z2, normal_w, layers, layers2): full-size maps and their 16 layers."""
     rng = np.random.default_rng(width * 1000 + height)
     cam = camera(width, height)
@@ -175,7 +176,7 @@ def synthetic(width, height):
     plateau = np.where((xx // 7 + yy // 5) % 2 == 0, F(3.0), F(3.4))                 # steps of 0.4
     z[0:h3, 2 * w3:W] = plateau[0:h3, 2 * w3:W]
     z[h3:h3 + H // 4, w3:w3 + W // 3] = F(cam.farZ)
-    z[0:16, 0:16] = F(0.0)
+    z[0:zero_patch, 0:zero_patch] = F(0.0)
     n = rng.normal(size=(H, W, 4)).astype(F)
     n[..., :3] /= np.linalg.norm(n[..., :3].astype(np.float64), axis=-1, keepdims=True).astype(F)
     z2 = (z + rng.uniform(0.05, 3.0, (H, W))).astype(F)

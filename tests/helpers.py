@@ -1,6 +1,7 @@
 """Shared test helpers: struct conversion between librsd and the oracle, the oracle side of a whole
 frame (G-buffer -> pass 1 -> SD trace -> pass 2), the SVAO parameter sweep of test_svao_params.py /
-test_gpu_svao_params.py, the frames of odd geometry of test_odd_geometry.py / test_gpu_odd_geometry.py, and the
+test_gpu_svao_params.py, the frames of odd geometry of test_odd_geometry.py / test_gpu_odd_geometry.py, the shapes,
+inputs and canary buffers of test_odd_passes.py / test_gpu_odd_passes.py (the passes outside the SVAO frame), and the
 grading of a fast-numerics frame against the exact oracle (test_gpu_numerics.py, test_gpu_svao_params.py)."""
 from __future__ import annotations
 
@@ -139,6 +140,175 @@ ODD_FRAMES = [
 # the SD map sizes the shapes are meant to have: lowResolution = ceil(fb / divisor), sdGuard = sd_guard_px // divisor
 ODD_SD_SIZES = {"odd_div3": (60, 39), "odd_div4": (34, 25), "no_guards": (66, 34), "tiny": (17, 13),
                 "one_over": (105, 73)}
+
+
+# ---- shapes of the passes outside the SVAO frame (test_odd_passes.py checks on the checkers alone that each of them
+# can show a fault; test_gpu_odd_passes.py runs the kernels on them)
+
+# (W, H) for the kernels with an 8 x 8 tile and one lane per pixel (rsd_gbuffer_raster, rsd_gbuffer_world,
+# rsd_depth_peel, rsd_rtao, rsd_sd_raster): one pixel, below a tile on both axes, exactly one tile, one over, one over
+# eight tiles and one over two.  W * H = 1, 21, 64, 81, 1105 around the 256 lanes of the flat kernels
+PIXEL_SHAPES = [(1, 1), (7, 3), (8, 8), (9, 9), (65, 17)]
+# (W, H) of the full-resolution frame for the kernels with a 64 x 4 block.  rsd_hbao works on 16 layers of
+# ceil(W / 4) x ceil(H / 4): 1 x 1 layers (at (3, 2) ten of the sixteen hold no pixel of the image), 2 x 2 layers,
+# layers of exactly one block, layers of 65 x 5
+BLOCK_SHAPES = [(1, 1), (3, 2), (5, 7), (256, 16), (257, 17)]
+# (W, H, guard band) for rsd_hbao, whose scissor on the layers is guard_band / 4: both guard bands of the existing
+# tests wherever they leave a texel inside the scissor ...
+HBAO_SHAPES = [(w, h, g) for w, h in BLOCK_SHAPES for g in (0, 8)
+               if (w + 3) // 4 > 2 * (g // 4) and (h + 3) // 4 > 2 * (g // 4)]
+# ... a scissor of 2 x -2 texels (nothing may be drawn) and a scissor of one texel per layer
+HBAO_EMPTY_SCISSOR = (40, 24, 16)
+HBAO_ONE_TEXEL_SCISSOR = (44, 44, 20)
+# rsd_temporal_depth_peel works at full resolution: the same sizes, and exactly one block and one over
+TEMPORAL_PEEL_SHAPES = BLOCK_SHAPES + [(64, 4), (65, 5)]
+
+
+# The camera of the tile kernels at PIXEL_SHAPES, for the opaque and the alpha scene of depth_peel_checker alike: from
+# a corner of the hall across its props, farZ pulled in (as tests/test_gpu_rtao.py does with CLIP_FAR) so that the
+# G-buffer misses a good part of every frame, the centre pixel -- the 1 x 1 frame -- hits, and a second layer lies
+# behind a good part of the hits; ODD_PASS_RTAO_MAX_T lets about a fifth of the spp = 1 rays hit.  Found by a search
+# over poses on the checkers alone; tests/test_odd_passes.py asserts the conditions.
+ODD_PASS_CAMERA = dict(pos=[14.93, 3.29, 10.8], target=[-8.88, 1.54, 1.21], up=[0.0, 1.0, 0.0])
+ODD_PASS_FAR = 18.0
+ODD_PASS_RTAO_MAX_T = 6.0
+# sd_raster_checker.BASE's AO radius is 6 on a 75 x 45 frame; these frames are up to five times smaller, and the
+# radius in pixels shrinks with them: 24 keeps pass 1 requesting SD rays (an interval and a stencil) on all of them
+ODD_PASS_SD_RADIUS = 24.0
+ODD_PASS_SD_DIVISORS = (1, 2, 3)
+ODD_PASS_SD_SAMPLES = (1, 4, 16)
+
+
+def odd_pass_case(oracle, checker_module, kind, size):
+    """checker_module.Case of `kind` at `size` seen by ODD_PASS_CAMERA with farZ = ODD_PASS_FAR (depth_peel_checker
+    and rtao_checker); sd_raster_checker's alpha case keeps its own BASE_CAMERA."""
+    from rsd.frame import look_at
+    c = checker_module.Case(oracle, kind, size)
+    if checker_module.__name__ != "sd_raster_checker":
+        c.cam = look_at(ODD_PASS_CAMERA["pos"], ODD_PASS_CAMERA["target"], ODD_PASS_CAMERA["up"], c.cfg)
+        c.cam.farZ = ODD_PASS_FAR
+        c.ocam = to_oracle(c.cam, oracle.Camera)
+    return c
+
+
+def hbao_odd_input(HB, width, height):
+    """hbao_checker.synthetic at a BLOCK_SHAPES size with a depth-0 patch that leaves most of a small frame alone,
+    and the radius of the parity test there: 1 from 16 rows on (every texel above one pixel, hbao_checker.radii),
+    16 / height below, which keeps 0.875 radius height / z >= 14 / 12 pixels."""
+    s = HB.synthetic(width, height, zero_patch=min(16, max(1, min(width, height) // 4)))
+    return s, max(1.0, 16.0 / height)
+
+
+def restride(image, stride):
+    """What a kernel that stored pixel (x, y) at y * stride + x would leave in the row-major buffer of `image`
+    (H x W x ...): the mutant "row stride taken from the padded width".  Elements past the buffer are dropped (the
+    canary's), elements never written are zero."""
+    h, w = image.shape[:2]
+    flat = np.zeros((max(h * stride, h * w),) + image.shape[2:], image.dtype)
+    for y in range(h):
+        flat[y * stride:y * stride + w] = image[y]
+    return flat[:h * w].reshape(image.shape)
+
+
+def roundup(v, m):
+    return -(-v // m) * m
+
+
+# rsd_rtao_pack: counts around its 256-lane block and the largest PIXEL_SHAPES frame
+PACK_COUNTS = [1, 255, 256, 257, 1105]
+PACK_SPECIALS = [np.nan, np.inf, 65520.0, 70000.0, -0.0]  # in the distance input: NaN, +inf, above 65504, -0
+
+
+def pack_inputs(count):
+    """(ambient in [0, 1], ray distance) of `count` elements; the distances start with as many of PACK_SPECIALS as
+    fit, then 65504 and the float just below 65520 (both round to 65504) where there is room."""
+    rng = np.random.default_rng(count)
+    amb = rng.random(count).astype(np.float32)
+    amb[:2] = [0.0, 1.0][:min(2, count)]
+    dist = rng.uniform(0.0, 12.0, count).astype(np.float32)
+    special = np.array(PACK_SPECIALS + [65504.0, np.nextafter(np.float32(65520.0), np.float32(0.0))], np.float32)
+    n = min(count, len(special))
+    dist[:n] = special[:n]
+    return amb, dist
+
+
+def pack_expected(amb, dist):
+    """floor(255 a + 0.5) and numpy's float16 rounding (round to nearest even), as tests/test_gpu_rtao.py's
+    test_graph states them; the float16 as its bits."""
+    with np.errstate(over="ignore"):
+        return (np.floor(amb.astype(np.float64) * 255.0 + 0.5).astype(np.uint8),
+                dist.astype(np.float16).view(np.uint16))
+
+
+def shape_id(s):
+    return "x".join(str(v) for v in s[:2]) + "".join(f"_g{v}" for v in s[2:])
+
+
+def band_rows(f, band_count):
+    """The 32-row groups of the visible rows and the 8-row tile rows of the SD map of the odd frame f, dealt to
+    band_count bands as rsd.h's band calls deal them (group g to band g % band_count): per band
+    (groups, SD tile rows)."""
+    sd_h = -(-(f.visible_h + 2 * f.guard) // f.divisor) + 2 * (f.sd_guard_px // f.divisor)
+    groups, tiles = range(-(-f.visible_h // 32)), range(-(-sd_h // 8))
+    return [([g for g in groups if g % band_count == b], [t for t in tiles if t % band_count == b])
+            for b in range(band_count)]
+
+
+def band_counts(f):
+    """The band counts the band tests run the odd frame f at: 2, 3 and one more than it has 32-row groups, which
+    leaves the last band without a row of pass 1 / pass 2."""
+    return [2, 3, -(-f.visible_h // 32) + 1]
+
+
+# ---- canaries: output buffers in the middle of a larger allocation of sentinel bytes
+
+SENTINEL = 0xA5      # every byte of the padding and of a pre-filled buffer
+PAD_ELEMENTS = 64    # at least this many elements of sentinel on either side of a view
+
+
+class Canary:
+    """A tensor of `shape` and `dtype` in the middle of a larger allocation full of sentinel bytes."""
+
+    def __init__(self, torch, shape, dtype, device):
+        item = torch.empty((), dtype=dtype).element_size()
+        self.n = int(np.prod(shape)) * item
+        self.pad = -(-PAD_ELEMENTS * item // 256) * 256   # a multiple of 256 bytes: the view keeps torch's alignment
+        self.raw = torch.full((self.n + 2 * self.pad,), SENTINEL, dtype=torch.uint8, device=device)
+        self.view = self.raw[self.pad:self.pad + self.n].view(dtype).view(tuple(shape))
+        assert self.view.data_ptr() == self.raw.data_ptr() + self.pad and self.pad >= PAD_ELEMENTS * item
+
+    def fill(self):
+        self.raw.fill_(SENTINEL)
+
+    def intact(self):
+        return bool((self.raw[:self.pad] == SENTINEL).all()) and bool((self.raw[self.pad + self.n:] == SENTINEL).all())
+
+    def numpy(self):
+        """The view's content on the host (a copy)."""
+        return self.view.cpu().numpy()
+
+    def untouched(self):
+        """Every byte of the view itself still holds the sentinel."""
+        return bool((self.raw[self.pad:self.pad + self.n] == SENTINEL).all())
+
+
+def sentinel_array(shape, dtype):
+    """The host twin of a pre-filled buffer."""
+    dtype = np.dtype(dtype)
+    return np.full(tuple(shape[:-1]) + (shape[-1] * dtype.itemsize,), SENTINEL, np.uint8).view(dtype)
+
+
+def canary(torch, shape, dtype, device="cuda"):
+    """A canary view of `shape` and `dtype`, pre-filled with the sentinel like its padding."""
+    return Canary(torch, shape, dtype, device)
+
+
+def assert_canaries_intact(torch, canaries, stage):
+    """After the work on the device has finished: no canary of the dict `canaries` (name -> Canary) has lost a
+    sentinel byte of its padding."""
+    torch.cuda.synchronize()
+    for name, c in canaries.items():
+        assert c.intact(), f"{stage}: a store outside the {name} buffer"
 
 
 def odd_second_pose(scene):

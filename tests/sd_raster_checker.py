@@ -36,8 +36,8 @@ _lib = None
 class Case(DP.Case):
     """depth_peel_checker's case; the alpha scene is seen by BASE_CAMERA, the opaque one by its own camera."""
 
-    def __init__(self, oracle, kind):
-        super().__init__(oracle, kind)
+    def __init__(self, oracle, kind, size=(W, H)):
+        super().__init__(oracle, kind, size)
         if kind == BASE["kind"]:
             from helpers import to_oracle
             from rsd.frame import look_at
@@ -98,10 +98,11 @@ def raster(oracle, lib, case, prm, depth, sd_w, sd_h, rmin=None, rmax=None, sten
     return out, dict(zip(COUNTERS, (int(v) for v in cnt)))
 
 
-def frame_config(divisor=1, radius=BASE["radius"], N=BASE["N"], cull=1, **kw):
-    """The W x H frame as SVAO's raster mode sees it: no guard bands, no SD jitter, exact numerics."""
+def frame_config(divisor=1, radius=BASE["radius"], N=BASE["N"], cull=1, size=(W, H), **kw):
+    """The frame of `size` (W x H by default) as SVAO's raster mode sees it: no guard bands, no SD jitter, exact
+    numerics."""
     from rsd.frame import FrameConfig
-    return FrameConfig(visible_w=W, visible_h=H, guard_band=0, divisor=divisor, sd_samples=N, sd_guard_px=0,
+    return FrameConfig(visible_w=size[0], visible_h=size[1], guard_band=0, divisor=divisor, sd_samples=N, sd_guard_px=0,
                        jitter=False, radius=radius, cull_mode=cull, numerics="exact", **kw)
 
 
@@ -125,10 +126,10 @@ class Frame:
 def oracle_frame(oracle, case, divisor=1, radius=BASE["radius"], N=BASE["N"], cull=1):
     from helpers import to_oracle
     from rsd.frame import make_vao, svao_params
-    cfg = frame_config(divisor, radius, N, cull)
+    cfg = frame_config(divisor, radius, N, cull, size=case.size)
     vao, sd_w, sd_h = make_vao(cfg)
     ovao, svp = to_oracle(vao, oracle.VAOData), to_oracle(svao_params(cfg), oracle.SVAOParams)
-    d, nw = oracle.gbuffer_raster(case.osc, case.ocam, W, H, cull)
+    d, nw = oracle.gbuffer_raster(case.osc, case.ocam, case.size[0], case.size[1], cull)
     z = oracle.linearize_depth(d, case.ocam.nearZ, case.ocam.farZ)
     n = oracle.compress_normals(nw, case.ocam)
     ao1, st, rmin, rmax = oracle.svao_pass1(case.ocam, ovao, svp, z, n, sd_w, sd_h)

@@ -23,39 +23,13 @@ import weakref
 import numpy as np
 import pytest
 
-from helpers import (ODD_FRAMES, grade, odd_frame, odd_frame_config, odd_second_pose, to_oracle,
-                     visible_region)
+from helpers import (ODD_FRAMES, PAD_ELEMENTS, SENTINEL, Canary, assert_canaries_intact, grade,  # noqa: F401
+                     odd_frame, odd_frame_config, odd_second_pose, sentinel_array, to_oracle, visible_region)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5      # every byte of the padding and of a pre-filled buffer
-PAD_ELEMENTS = 64    # at least this many elements of sentinel on either side of a view
 SHAPES = [f.name for f in ODD_FRAMES]
 OUTPUTS = ("depth", "normals", "ao", "stencil", "ray_min", "ray_max", "sd")
-
-
-class Canary:
-    """A tensor of `shape` and `dtype` in the middle of a larger allocation full of sentinel bytes."""
-
-    def __init__(self, torch, shape, dtype, device):
-        item = torch.empty((), dtype=dtype).element_size()
-        self.n = int(np.prod(shape)) * item
-        self.pad = -(-PAD_ELEMENTS * item // 256) * 256   # a multiple of 256 bytes: the view keeps torch's alignment
-        self.raw = torch.full((self.n + 2 * self.pad,), SENTINEL, dtype=torch.uint8, device=device)
-        self.view = self.raw[self.pad:self.pad + self.n].view(dtype).view(tuple(shape))
-        assert self.view.data_ptr() == self.raw.data_ptr() + self.pad and self.pad >= PAD_ELEMENTS * item
-
-    def fill(self):
-        self.raw.fill_(SENTINEL)
-
-    def intact(self):
-        return bool((self.raw[:self.pad] == SENTINEL).all()) and bool((self.raw[self.pad + self.n:] == SENTINEL).all())
-
-
-def sentinel_array(shape, dtype):
-    """The host twin of a pre-filled buffer."""
-    dtype = np.dtype(dtype)
-    return np.full(tuple(shape[:-1]) + (shape[-1] * dtype.itemsize,), SENTINEL, np.uint8).view(dtype)
 
 
 @pytest.fixture(scope="module")
@@ -97,9 +71,7 @@ def _renderer(ctx, f, **kw):
 
 
 def _intact(ctx, r, stage):
-    ctx.torch.cuda.synchronize()
-    for name, c in r.canaries.items():
-        assert c.intact(), f"{stage}: a store outside the {name} buffer"
+    assert_canaries_intact(ctx.torch, r.canaries, stage)
 
 
 def _structs(ctx, r):
