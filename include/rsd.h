@@ -335,6 +335,45 @@ rsd_status rsd_scene_dynamic_info_get(const rsd_scene* scene, rsd_scene_dynamic_
 rsd_status rsd_bvh_refit(const void* bvh, uint64_t bvh_bytes, uint32_t tri_offset, const uint32_t* indices,
                          uint32_t triangle_count, const float* positions, uint32_t vertex_count, void* dst);
 
+/* --- animated scenes: a rig and a pose kernel (DESIGN.md 4 "Animated scenes") -------------------
+ * A rig names `count` vertices of a dynamic scene and gives each four (matrix id, weight) influences into a
+ * table of matrix_count matrices; rigid node animation and linear-blend skinning are the same thing here (a
+ * rigid vertex is ids (m, 0, 0, 0), weights (1, 0, 0, 0)).  All pointers are host memory. */
+typedef struct {
+    uint32_t count;              /* animated vertices (0 is legal: a rig that moves nothing) */
+    uint32_t matrix_count;       /* matrices a pose supplies; > 0 when count > 0 */
+    const uint32_t* vertex_ids;  /* uint32[count], each < vertex_count, none twice */
+    const uint32_t* matrix_ids;  /* uint32[count][4], each < matrix_count (slots of weight 0 included) */
+    const float* weights;        /* float[count][4], used as given: no normalisation */
+    const float* rest_positions; /* float3[count]: the positions the matrices act on, or NULL: the scene's
+                                  * positions of the animated vertices at the moment of the call */
+} rsd_rig_desc;
+/* Attach (or replace) the rig of a scene of rsd_scene_upload_dynamic; RSD_ERR_INVALID_ARG on any other scene
+ * and on a rig that breaks a rule above (checked on the host, nothing is issued).  Synchronous, and the only
+ * call of this group that allocates: it waits for the device, copies the rig and the rest positions to it
+ * and allocates the scene's matrix table. */
+rsd_status rsd_scene_attach_rig(rsd_scene* scene, const rsd_rig_desc* rig);
+/* Pose the animated vertices and refit.  matrices: float[matrix_count][12], the first three rows of each
+ * matrix, row-major, translation in column 3; from device memory (matrices_on_device != 0, read in place) or
+ * from host memory, which is copied asynchronously on `stream` and must stay alive until that copy has run.
+ * Stream-ordered, no host wait, no allocation: the optional copy, the pose kernel (one lane per animated
+ * vertex; other vertices are neither read nor written) and rsd_scene_update_positions' two launches; the
+ * entry grid is marked stale and rsd_scene_dynamic_info.updates counts the call.  Per animated vertex, every
+ * product and sum rounded to float32 on its own (no FMA), for each of the 12 elements e:
+ *   B[e] = ((M[i0][e] * w0 + M[i1][e] * w1) + M[i2][e] * w2) + M[i3][e] * w3
+ * and for each row r:  out[r] = ((B[r][0] * x + B[r][1] * y) + B[r][2] * z) + B[r][3]   with (x, y, z) the
+ * vertex's rest position.  RSD_ERR_INVALID_ARG without a rig or when matrix_count is not the rig's. */
+rsd_status rsd_scene_update_pose(rsd_scene* scene, const float* matrices, uint32_t matrix_count,
+                                 uint32_t matrices_on_device, rsd_stream stream);
+typedef struct {
+    uint32_t attached;      /* 1: the scene has a rig */
+    uint32_t count;         /* animated vertices */
+    uint32_t matrix_count;  /* matrices of a pose */
+    uint32_t reserved;
+    uint64_t rig_bytes;     /* device bytes of the rig, its rest positions and the matrix table */
+} rsd_scene_rig_info;
+rsd_status rsd_scene_rig_info_get(const rsd_scene* scene, rsd_scene_rig_info* out);
+
 /* --- host helpers (no GPU work) ---------------------------------------------------- */
 /* RAY_CONE_SPREAD of the SD pass (StochasticDepthMapRT.cpp:266-267): Camera::
  * computeScreenSpacePixelSpreadAngle(height) (Camera.cpp:296-301) with the fovY of the 24 mm

@@ -58,6 +58,10 @@ rsd_status rsd_graph_set_scene(rsd_graph* g, rsd_scene* scene, const rsd_camera*
  * motion vectors) know the camera's motion only, not the geometry's. */
 rsd_status rsd_graph_update_scene_positions(rsd_graph* g, const float* positions, uint32_t vertex_count,
                                             uint32_t positions_on_device, rsd_stream stream);
+/* The same for a pose of the scene's rig (rsd.h rsd_scene_update_pose; the rig was attached to the scene with
+ * rsd_scene_attach_rig). */
+rsd_status rsd_graph_update_scene_pose(rsd_graph* g, const float* matrices, uint32_t matrix_count,
+                                       uint32_t matrices_on_device, rsd_stream stream);
 /* external input bound to "pass.field" (caller-owned device memory) */
 rsd_status rsd_graph_set_input(rsd_graph* g, const char* name, const rsd_texture* tex);
 rsd_status rsd_graph_compile(rsd_graph* g, uint32_t width, uint32_t height, rsd_stream stream);

@@ -120,6 +120,16 @@ rsd_status rsd_graph_update_scene_positions(rsd_graph* g, const float* positions
     return rsd_scene_update_positions(g->scene.scene, positions, vertex_count, positions_on_device, stream);
 }
 
+rsd_status rsd_graph_update_scene_pose(rsd_graph* g, const float* matrices, uint32_t matrix_count,
+                                       uint32_t matrices_on_device, rsd_stream stream) {
+    if (!g) return nullArg("rsd_graph_update_scene_pose");
+    if (!g->hasScene || !g->scene.scene) {
+        rsd::set_error("rsd_graph_update_scene_pose: no scene set");
+        return RSD_ERR_INVALID_ARG;
+    }
+    return rsd_scene_update_pose(g->scene.scene, matrices, matrix_count, matrices_on_device, stream);
+}
+
 rsd_status rsd_graph_set_input(rsd_graph* g, const char* name, const rsd_texture* tex) {
     if (!g || !name || !tex || !tex->ptr) return nullArg("rsd_graph_set_input");
     return guarded("rsd_graph_set_input", [&] {

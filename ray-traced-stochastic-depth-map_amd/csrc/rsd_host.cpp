@@ -496,6 +496,121 @@ extern "C" rsd_status rsd_scene_update_subset(rsd_scene* s, const uint32_t* d_ve
     return rsd::refit_enqueue(s, hs);
 }
 
+extern "C" rsd_status rsd_scene_attach_rig(rsd_scene* s, const rsd_rig_desc* rig) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_attach_rig"); st != RSD_OK) return st;
+    auto refuse = [](const std::string& why) {
+        set_error("rsd_scene_attach_rig: " + why);
+        return RSD_ERR_INVALID_ARG;
+    };
+    if (!rig) return refuse("null rig");
+    const uint32_t n = rig->count, nm = rig->matrix_count, nv = s->vertex_count;
+    if (n && (!rig->vertex_ids || !rig->matrix_ids || !rig->weights)) return refuse("null argument");
+    if (n && !nm) return refuse("matrix_count is 0 with animated vertices");
+    {
+        std::vector<uint8_t> seen(nv, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t v = rig->vertex_ids[i];
+            if (v >= nv)
+                return refuse("vertex id " + std::to_string(v) + " is out of range of vertex_count " + std::to_string(nv));
+            if (seen[v]) return refuse("vertex " + std::to_string(v) + " is named twice");
+            seen[v] = 1;
+            for (int k = 0; k < 4; ++k)
+                if (rig->matrix_ids[4 * (size_t)i + k] >= nm)
+                    return refuse("matrix id " + std::to_string(rig->matrix_ids[4 * (size_t)i + k]) +
+                                  " is out of range of matrix_count " + std::to_string(nm));
+        }
+    }
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    // synchronous: updates enqueued so far have run before the rest positions are read and before the rig
+    // a pose in flight reads is freed
+    RSD_HIP(hipDeviceSynchronize());
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t oVid = 0, oMid = al(4 * (size_t)n), oW = oMid + al(16 * (size_t)n), oRest = oW + al(16 * (size_t)n),
+                 oMat = oRest + al(12 * (size_t)n), total = oMat + al(48 * (size_t)nm);
+    std::vector<float> rest(3 * (size_t)n);
+    if (n && rig->rest_positions) {
+        std::memcpy(rest.data(), rig->rest_positions, 12 * (size_t)n);
+    } else if (n) {
+        std::vector<float> all(3 * (size_t)nv);
+        RSD_HIP(hipMemcpy(all.data(), s->dyn.positions, 12 * (size_t)nv, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) rest[3 * (size_t)i + k] = all[3 * (size_t)rig->vertex_ids[i] + k];
+    }
+    char* d = nullptr;
+    hipError_t e = hipMalloc(&d, total ? total : 256);
+    if (e == hipSuccess && total) e = hipMemset(d, 0, total);
+    if (e == hipSuccess && n) e = hipMemcpy(d + oVid, rig->vertex_ids, 4 * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(d + oMid, rig->matrix_ids, 16 * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(d + oW, rig->weights, 16 * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(d + oRest, rest.data(), 12 * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return rsd::hip_fail(e, "rsd_scene_attach_rig");
+    }
+    if (s->d_rig) {
+        (void)hipFree(s->d_rig);
+        s->device_bytes -= s->rig_bytes;
+    }
+    s->d_rig = d;
+    s->rig.count = n;
+    s->rig.matrix_count = nm;
+    s->rig.vertex_ids = reinterpret_cast<uint32_t*>(d + oVid);
+    s->rig.matrix_ids = reinterpret_cast<uint32_t*>(d + oMid);
+    s->rig.weights = reinterpret_cast<float*>(d + oW);
+    s->rig.rest = reinterpret_cast<float*>(d + oRest);
+    s->rig.matrices = reinterpret_cast<float*>(d + oMat);
+    s->rig_bytes = total ? total : 256;
+    s->device_bytes += s->rig_bytes;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_scene_update_pose(rsd_scene* s, const float* matrices, uint32_t matrix_count,
+                                            uint32_t matrices_on_device, rsd_stream stream) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_update_pose"); st != RSD_OK) return st;
+    if (!s->d_rig) {
+        set_error("rsd_scene_update_pose: the scene has no rig (rsd_scene_attach_rig)");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (matrix_count != s->rig.matrix_count) {
+        set_error("rsd_scene_update_pose: matrix_count " + std::to_string(matrix_count) + " is not the rig's " +
+                  std::to_string(s->rig.matrix_count));
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (!matrices && matrix_count) {
+        set_error("rsd_scene_update_pose: null matrices");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (matrices_on_device && reinterpret_cast<uintptr_t>(matrices) % 16 != 0) {
+        set_error("rsd_scene_update_pose: device matrices must be 16-byte aligned");
+        return RSD_ERR_INVALID_ARG;
+    }
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    hipStream_t hs = (hipStream_t)stream;
+    const float* d_matrices = matrices;
+    if (!matrices_on_device) {
+        if (matrix_count)
+            RSD_HIP(hipMemcpyAsync(s->rig.matrices, matrices, 48 * (size_t)matrix_count, hipMemcpyHostToDevice, hs));
+        d_matrices = s->rig.matrices;
+    }
+    if (rsd_status st = rsd::pose_enqueue(s, d_matrices, hs); st != RSD_OK) return st;
+    s->entry_stale = s->entry_stale || s->d_entry != nullptr;
+    ++s->updates;
+    return rsd::refit_enqueue(s, hs);
+}
+
+extern "C" rsd_status rsd_scene_rig_info_get(const rsd_scene* s, rsd_scene_rig_info* out) {
+    if (!s || !out) {
+        set_error("rsd_scene_rig_info_get: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    out->attached = s->d_rig ? 1u : 0u;
+    out->count = s->rig.count;
+    out->matrix_count = s->rig.matrix_count;
+    out->reserved = 0;
+    out->rig_bytes = s->rig_bytes;
+    return RSD_OK;
+}
+
 extern "C" rsd_status rsd_scene_rebuild_entry_grid(rsd_scene* s) {
     if (!s) {
         set_error("rsd_scene_rebuild_entry_grid: null scene");
@@ -616,6 +731,7 @@ extern "C" void rsd_scene_release(rsd_scene* s) {
     (void)hipFree(s->d_entry);
     (void)hipFree(s->d_rtao_table);
     (void)hipFree(s->d_dyn);
+    (void)hipFree(s->d_rig);
     delete s;
 }
 

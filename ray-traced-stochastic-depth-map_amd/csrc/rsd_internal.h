@@ -73,6 +73,17 @@ struct DynamicData {
     uint32_t* arrive = nullptr;   // per wide node: inner children arrived in this refit (zero between refits)
     uint32_t* tight = nullptr;    // per wide node: its tight box as keys, lo[3] hi[3] (bvh_refit.h)
 };
+
+// The rig of a dynamic scene (rsd_scene_attach_rig, csrc/skinning.hip): pointers into rsd_scene.d_rig, one
+// allocation.  Every id in it was checked on the host at attach.
+struct RigData {
+    uint32_t count = 0, matrix_count = 0;
+    uint32_t* vertex_ids = nullptr;  // uint32[count]
+    uint32_t* matrix_ids = nullptr;  // uint32[count][4], 16-byte aligned
+    float* weights = nullptr;        // float[count][4], 16-byte aligned
+    float* rest = nullptr;           // float3[count]: what the matrices act on
+    float* matrices = nullptr;       // float[matrix_count][12]: where a pose from host memory is copied
+};
 }  // namespace rsd
 
 struct rsd_scene {
@@ -108,6 +119,10 @@ struct rsd_scene {
     // an update moved geometry since the entry grid was built: traces pass no table (the root-start path)
     // until rsd_scene_rebuild_entry_grid
     bool entry_stale = false;
+    // animated scenes (rsd_scene_attach_rig): d_rig == null without a rig
+    void* d_rig = nullptr;
+    rsd::RigData rig;
+    uint64_t rig_bytes = 0;
 };
 
 namespace rsd {
@@ -119,6 +134,8 @@ rsd_status hip_fail(hipError_t e, const char* what);
 rsd_status refit_scatter_enqueue(rsd_scene* s, const uint32_t* d_ids, const float* d_positions, uint32_t count,
                                  hipStream_t st);
 rsd_status refit_enqueue(rsd_scene* s, hipStream_t st);
+// skinning.hip: pose the rig's vertices into the scene's position copy from `d_matrices` (float[matrix_count][12])
+rsd_status pose_enqueue(rsd_scene* s, const float* d_matrices, hipStream_t st);
 
 // sd_trace.hip: the stratified coverage-mask tables of N samples on HIP device `dev` (indices [N + 1], look-up
 // table [2^N]), uploaded once per (device, N) and never freed; shared by the SD trace and sd_raster.hip

@@ -62,6 +62,16 @@ class SceneDynamicInfo(C.Structure):  # rsd_scene_dynamic_info
                 ("dynamic_bytes", C.c_uint64)]
 
 
+class RigDesc(C.Structure):  # rsd_rig_desc
+    _fields_ = [("count", C.c_uint32), ("matrix_count", C.c_uint32), ("vertex_ids", C.c_void_p),
+                ("matrix_ids", C.c_void_p), ("weights", C.c_void_p), ("rest_positions", C.c_void_p)]
+
+
+class SceneRigInfo(C.Structure):  # rsd_scene_rig_info
+    _fields_ = [("attached", C.c_uint32), ("count", C.c_uint32), ("matrix_count", C.c_uint32),
+                ("reserved", C.c_uint32), ("rig_bytes", C.c_uint64)]
+
+
 class Camera(C.Structure):
     _fields_ = [("posW", C.c_float * 3), ("nearZ", C.c_float),
                 ("U", C.c_float * 3), ("farZ", C.c_float),
@@ -277,7 +287,8 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_band_frame_release", "rsd_band_frame_set_split", "rsd_depth_peel", "rsd_gbuffer_world",
            "rsd_rtao", "rsd_rtao_sample_table", "rsd_rtao_ray_t_max", "rsd_rtao_pack", "rsd_hbao",
            "rsd_hbao_noise_table", "rsd_sd_raster", "rsd_scene_upload_dynamic", "rsd_scene_update_positions",
-           "rsd_scene_update_subset", "rsd_scene_rebuild_entry_grid", "rsd_scene_dynamic_info_get", "rsd_bvh_refit"]
+           "rsd_scene_update_subset", "rsd_scene_rebuild_entry_grid", "rsd_scene_dynamic_info_get", "rsd_bvh_refit",
+           "rsd_scene_attach_rig", "rsd_scene_update_pose", "rsd_scene_rig_info_get"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -295,7 +306,7 @@ GRAPH_EXPORTS = ["rsd_graph_create", "rsd_graph_destroy", "rsd_graph_create_pass
                  "rsd_deinterleave", "rsd_interleave", "rsd_ray_min_max_length", "rsd_temporal_depth_peel",
                  "rsd_cross_bilateral_blur_src", "rsd_ao_guided_blur", "rsd_ao_first_channel", "rsd_ao_variance_fix",
                  "rsd_convnet_create", "rsd_convnet_load_dir", "rsd_convnet_release", "rsd_convnet_get_info",
-                 "rsd_convnet_run", "rsd_graph_update_scene_positions"]
+                 "rsd_convnet_run", "rsd_graph_update_scene_positions", "rsd_graph_update_scene_pose"]
 GRAPH_SIZE_EXPORTS = ["rsd_convnet_scratch_bytes"]
 
 FMT_R32F, FMT_RG32F, FMT_RGBA32F, FMT_R16U, FMT_R8U, FMT_R8UNORM, FMT_R32U, FMT_UNKNOWN = range(8)
@@ -343,6 +354,12 @@ def lib():
         L.rsd_scene_rebuild_entry_grid.argtypes = [vp]
         L.rsd_scene_dynamic_info_get.restype = st
         L.rsd_scene_dynamic_info_get.argtypes = [vp, C.POINTER(SceneDynamicInfo)]
+        L.rsd_scene_attach_rig.restype = st
+        L.rsd_scene_attach_rig.argtypes = [vp, C.POINTER(RigDesc)]
+        L.rsd_scene_update_pose.restype = st
+        L.rsd_scene_update_pose.argtypes = [vp, vp, u32, u32, vp]
+        L.rsd_scene_rig_info_get.restype = st
+        L.rsd_scene_rig_info_get.argtypes = [vp, C.POINTER(SceneRigInfo)]
         L.rsd_bvh_refit.restype = st
         L.rsd_bvh_refit.argtypes = [vp, C.c_uint64, u32, vp, u32, vp, u32, vp]
         L.rsd_ray_cone_spread.restype = f32
@@ -474,6 +491,7 @@ def lib():
             "rsd_graph_mark_output": [vp, cs],
             "rsd_graph_set_scene": [vp, vp, C.POINTER(Camera)],
             "rsd_graph_update_scene_positions": [vp, vp, u32, u32, vp],
+            "rsd_graph_update_scene_pose": [vp, vp, u32, u32, vp],
             "rsd_graph_set_input": [vp, cs, tp],
             "rsd_graph_compile": [vp, u32, u32, vp],
             "rsd_graph_execute": [vp, vp],

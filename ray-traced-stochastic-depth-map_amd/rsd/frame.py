@@ -235,6 +235,9 @@ class GpuScene:
                       "rsd_scene_upload_alpha")
             del keep
         self.h = h
+        self.rig = None
+        if dynamic and getattr(scene, "rig", None) is not None:
+            self.attach_rig(scene.rig)
         self.info = abi.SceneInfo()
         abi.check(abi.lib().rsd_scene_info_get(h, C.byref(self.info)), "rsd_scene_info_get")
 
@@ -288,6 +291,42 @@ class GpuScene:
         abi.check(abi.lib().rsd_scene_update_subset(self.h, ids.data_ptr(), positions.data_ptr(), ids.numel(),
                                                     self._stream(stream)), "rsd_scene_update_subset")
         self._keep = (ids, positions)
+
+    def attach_rig(self, rig):
+        """rsd_scene_attach_rig: `rig` (rsd.animation.Rig) names the vertices update_pose / animate move.  Synchronous;
+        replaces an earlier rig.  Without rig.rest the rest pose is the scene's positions of this moment."""
+        d = abi.RigDesc(rig.count, rig.matrix_count, rig.vertex_ids.ctypes.data, rig.matrix_ids.ctypes.data,
+                        rig.weights.ctypes.data, rig.rest.ctypes.data if rig.rest is not None else None)
+        abi.check(abi.lib().rsd_scene_attach_rig(self.h, C.byref(d)), "rsd_scene_attach_rig")
+        self.rig = rig
+
+    def update_pose(self, matrices, stream=None):
+        """Pose the rig's vertices and refit (rsd_scene_update_pose): `matrices` is float32 [matrix_count, 12] -- the
+        first three rows of each matrix, row-major -- as a numpy array (copied from the host on the stream: it is
+        kept alive here until the next update) or a contiguous float32 torch tensor on the scene's device."""
+        if isinstance(matrices, np.ndarray) or not hasattr(matrices, "data_ptr"):
+            m = np.ascontiguousarray(matrices, np.float32)
+            ptr, n, on_device = m.ctypes.data, m.size // 12, 0
+        else:
+            m = matrices.contiguous()
+            if not m.is_cuda or str(m.dtype) != "torch.float32":
+                raise ValueError("update_pose: a tensor must be float32 and on the GPU")
+            ptr, n, on_device = m.data_ptr(), m.numel() // 12, 1
+        abi.check(abi.lib().rsd_scene_update_pose(self.h, ptr, n, on_device, self._stream(stream)),
+                  "rsd_scene_update_pose")
+        self._keep = m
+
+    def animate(self, t, stream=None):
+        """The scene at animation time t: the rig's controller is evaluated on the host (rsd.animation) and its
+        matrices go to update_pose."""
+        if self.rig is None:
+            raise ValueError("animate: the scene has no rig")
+        self.update_pose(self.rig.matrices(t), stream)
+
+    def rig_info(self) -> abi.SceneRigInfo:
+        d = abi.SceneRigInfo()
+        abi.check(abi.lib().rsd_scene_rig_info_get(self.h, C.byref(d)), "rsd_scene_rig_info_get")
+        return d
 
     def rebuild_entry_grid(self):
         """Make the segment entry grid current again after updates (rsd_scene_rebuild_entry_grid; synchronous)."""
@@ -433,6 +472,11 @@ class Renderer:
         self.gscene.update_positions(positions, stream=self.stream)
         host = positions.detach().cpu().numpy() if hasattr(positions, "data_ptr") else positions
         self.scene = dataclasses.replace(self.scene, positions=np.array(host, np.float32).reshape(-1, 3))
+
+    def animate(self, t):
+        """The scene at animation time t (GpuScene.animate on this renderer's stream).  self.scene.positions keeps
+        the upload's positions: the posed ones exist on the device only."""
+        self.gscene.animate(t, stream=self.stream)
 
     @property
     def stream(self):

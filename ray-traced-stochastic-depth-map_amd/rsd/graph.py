@@ -97,8 +97,11 @@ class RenderGraph:
     addPass, addEdge, markOutput = add_pass, add_edge, mark_output
 
     # -- application surface
-    def set_scene(self, scene_handle, camera: abi.Camera):
+    def set_scene(self, scene_handle, camera: abi.Camera, rig=None):
+        """rig: the rsd.animation.Rig attached to the scene (GpuScene.rig), for animate(t)."""
         abi.check(self._L.rsd_graph_set_scene(self._h, scene_handle, C.byref(camera)), "set_scene")
+        if rig is not None:
+            self._rig = rig
 
     def update_positions(self, positions, stream=None):
         """Move the vertices of the graph's scene -- a dynamic one, GpuScene(dev, scene, dynamic=True), given to
@@ -115,6 +118,27 @@ class RenderGraph:
         abi.check(self._L.rsd_graph_update_scene_positions(self._h, ptr, n, on_device, stream),
                   "rsd_graph_update_scene_positions")
         self._keep = [pos]
+
+    def update_pose(self, matrices, stream=None):
+        """Pose the rig of the graph's scene on `stream` (rsd_graph_update_scene_pose): matrices is float32
+        [matrix_count, 12], a numpy array (kept alive here until the next update) or a torch tensor on the device."""
+        import numpy as np
+        if hasattr(matrices, "data_ptr"):
+            m = matrices.contiguous()
+            ptr, n, on_device = m.data_ptr(), m.numel() // 12, 1
+        else:
+            m = np.ascontiguousarray(matrices, np.float32)
+            ptr, n, on_device = m.ctypes.data, m.size // 12, 0
+        abi.check(self._L.rsd_graph_update_scene_pose(self._h, ptr, n, on_device, stream), "rsd_graph_update_scene_pose")
+        self._keep = [m]
+
+    def animate(self, t, stream=None):
+        """The scene at animation time t: the rig given to set_scene evaluates its controller on the host and the
+        pose goes to update_pose; the next execute on that stream renders it."""
+        rig = getattr(self, "_rig", None)
+        if rig is None:
+            raise ValueError("animate: set_scene was given no rig")
+        self.update_pose(rig.matrices(t), stream)
 
     def set_input(self, name: str, ptr: int, width: int, height: int, fmt: int, layers: int = 1):
         t = abi.Texture(C.c_void_p(ptr), width, height, layers, fmt, 0)

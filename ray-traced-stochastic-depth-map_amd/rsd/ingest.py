@@ -25,6 +25,7 @@ from pathlib import Path
 
 import numpy as np
 
+from . import animation as anim
 from .scenes import FLAG_ALPHA_MASK, FLAG_DOUBLE_SIDED, NO_TEXTURE, AlphaMaterials, Scene
 
 
@@ -55,6 +56,11 @@ class SceneBuilder:
         self.materials: list[Material] = []
         self.meshes: list[Mesh] = []
         self.instances: list[tuple[int, np.ndarray]] = []
+        # the scene graph and its animations (animated scenes, rsd.animation): (local matrix, parent) per node,
+        # parents first; the node an instance hangs on, or None for one placed by a matrix alone
+        self.nodes: list[tuple[np.ndarray, int]] = []
+        self.animations: list[anim.Animation] = []
+        self.instance_nodes: list[int | None] = []
         self.camera = {"pos": [0.0, 0.0, 5.0], "target": [0.0, 0.0, 0.0], "up": [0.0, 1.0, 0.0]}
 
     def add_material(self, m: Material) -> int:
@@ -73,23 +79,67 @@ class SceneBuilder:
         self.meshes.append(mesh)
         return len(self.meshes) - 1
 
-    def add_instance(self, mesh_id: int, transform=None):
+    def add_node(self, matrix=None, parent: int = anim.INVALID_ID) -> int:
+        m = np.eye(4, dtype=np.float32) if matrix is None else np.asarray(matrix, np.float32).reshape(4, 4)
+        if parent != anim.INVALID_ID and not 0 <= parent < len(self.nodes):
+            raise ValueError(f"add_node: parent {parent} does not exist")
+        self.nodes.append((m, parent))
+        return len(self.nodes) - 1
+
+    def add_instance(self, mesh_id: int, transform=None, node: int | None = None):
+        """node: the scene-graph node the instance hangs on (its world matrix at rest is `transform`); it matters
+        only when that node or one above it is animated."""
         t = np.eye(4, dtype=np.float32) if transform is None else np.asarray(transform, np.float32).reshape(4, 4)
+        if node is not None and not 0 <= node < len(self.nodes):
+            raise ValueError(f"add_instance: node {node} does not exist")
         self.instances.append((mesh_id, t))
+        self.instance_nodes += [None] * (len(self.instances) - 1 - len(self.instance_nodes)) + [node]
 
     def set_camera(self, pos, target, up=(0.0, 1.0, 0.0)):
         self.camera = {"pos": list(map(float, pos)), "target": list(map(float, target)), "up": list(map(float, up))}
 
-    def build(self, name: str = "scene") -> Scene:
+    def build(self, name: str = "scene", animated: bool = True) -> Scene:
+        """animated=False ignores the animations: the still scene at the nodes' own matrices, without a rig.
+
+        With animations (DESIGN.md 4 "Animated scenes") the Scene gets a `rig`: every instance whose node chain holds
+        an animated node contributes its vertices, each rigid under that instance's node.  The rig's rest positions
+        are the mesh's object-space positions, and the soup holds them posed by the node's global matrix at t = 0
+        with rsd_scene_update_pose's arithmetic, so the pose at t = 0 reproduces the soup bit for bit.  The winding
+        unification below is decided by that matrix once: an animation that flips the determinant's sign later
+        keeps these indices and flags."""
         if not self.materials:
             self.add_material(Material())
         pos, ind, flg, uv, mat = [], [], [], [], []
         nv = 0
-        for mesh_id, T in self.instances:
+        controller, moving, rest_pose, matrix_of = None, set(), None, {}
+        rig_ids, rig_mats, rig_rest = [], [], []
+        if animated and self.animations:
+            controller = anim.AnimationController(self.nodes, self.animations)
+            moving = controller.animated_nodes()
+            nodes_of = self.instance_nodes + [None] * (len(self.instances) - len(self.instance_nodes))
+            for n in nodes_of:
+                if n in moving and n not in matrix_of:
+                    matrix_of[n] = len(matrix_of)
+            controller.matrix_nodes = list(matrix_of)
+            rest_pose = controller.matrices(0.0)
+        for k, (mesh_id, T) in enumerate(self.instances):
             m = self.meshes[mesh_id]
             mt = self.materials[m.material]
-            # object -> world in float32 (transformPoint)
-            p = (m.positions @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+            node = self.instance_nodes[k] if controller is not None and k < len(self.instance_nodes) else None
+            if node is not None and node in moving:
+                slot = matrix_of[node]
+                T = np.eye(4, dtype=np.float32)
+                T[:3, :] = rest_pose[slot].reshape(3, 4)
+                one = np.zeros((len(m.positions), 4), np.float32)
+                one[:, 0] = 1.0
+                p = anim.pose_positions(m.positions, np.full((len(m.positions), 4), [slot, 0, 0, 0], np.uint32), one,
+                                        rest_pose)
+                rig_ids.append(np.arange(nv, nv + len(p), dtype=np.uint32))
+                rig_mats.append(np.full(len(p), slot, np.uint32))
+                rig_rest.append(m.positions)
+            else:
+                # object -> world in float32 (transformPoint)
+                p = (m.positions @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
             tri = m.indices.astype(np.int64)
             cw = m.front_face_cw != bool(np.linalg.det(T[:3, :3].astype(np.float64)) < 0.0)
             if cw:  # unifyTriangleWinding: counter-clockwise front faces everywhere
@@ -118,7 +168,12 @@ class SceneBuilder:
                                    np.array([m.alpha_threshold for m in self.materials], np.float32),
                                    np.array([m.alpha for m in self.materials], np.float32),
                                    np.array(tex_of, np.uint32), textures)
-        return Scene(name, positions, indices, flags, self.camera, alpha)
+        rig = None
+        if controller is not None:
+            cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)  # noqa: E731
+            rig = anim.Rig.rigid(cat(rig_ids, 0, np.uint32), cat(rig_mats, 0, np.uint32), len(matrix_of),
+                                 rest=cat(rig_rest, (0, 3), np.float32), controller=controller)
+        return Scene(name, positions, indices, flags, self.camera, alpha, rig)
 
 
 # ---------------------------------------------------------------------------------- images

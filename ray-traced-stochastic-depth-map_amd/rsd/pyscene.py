@@ -19,7 +19,11 @@ scope.  The bindings this module mirrors, with the geometry they produce:
   addTriangleMesh, addMaterial, getMaterial, replaceMaterial, loadMaterialTexture, addNode
   (world = parent world * local), addMeshInstance, addCamera (the first camera is the scene's).
 
-What the SD trace cannot see is accepted and dropped: lights, env maps, grid volumes, animations
+* `Animation` (rsd.animation, Scene/Animation/Animation.cpp) with `sceneBuilder.addAnimation` / `createAnimation`:
+  the nodes and animations are kept, and an instance below an animated node becomes part of the scene's rig
+  (rsd.ingest.SceneBuilder.build).
+
+What the SD trace cannot see is accepted and dropped: lights, env maps, grid volumes
 and procedural geometry (SDF grids, custom primitives) -- the SD rays skip procedural primitives
 (StochasticDepthMapRT.rt.slang:85 RAY_FLAG_SKIP_PROCEDURAL_PRIMITIVES).  glTF / USD / PBRT / ASCII FBX
 imports raise (no importer for them in this image)."""
@@ -31,6 +35,7 @@ from pathlib import Path
 import numpy as np
 
 from . import fbx, ingest
+from .animation import Animation
 
 F32 = np.float32
 INVALID_ID = 0xFFFFFFFF  # NodeID::kInvalidID
@@ -172,6 +177,7 @@ class Transform:
 
     translation = property(lambda s: s._t.copy().view(_Vec), lambda s, v: setattr(s, "_t", _f3(v)))
     scaling = property(lambda s: s._s.copy().view(_Vec), lambda s, v: setattr(s, "_s", _f3(v)))
+    rotation = property(lambda s: s._q.copy().view(_Vec))  # the quaternion (x, y, z, w): Transform::getRotation
 
     def _set_euler(self, v):
         self._q = _quat_from_euler(_f3(v))
@@ -437,7 +443,7 @@ Material = StandardMaterial  # StandardMaterial.cpp:225
 
 class _Inert:
     """Bindings whose objects never reach the SD trace (lights, env maps, volumes, SDF grids,
-    animations, settings): attributes are stored, methods accept anything."""
+    settings): attributes are stored, methods accept anything."""
 
     def __init__(self, *args, **kw):
         object.__setattr__(self, "_attrs", dict(kw))
@@ -479,6 +485,7 @@ class Camera:
         self.position = float3(0, 0, 1)
         self.target = float3(0, 0, 0)
         self.up = float3(0, 1, 0)
+        self.nodeID = INVALID_ID  # Animatable: set by sceneBuilder.createAnimation (the SD camera itself stays put)
         self.focalLength = 21.0
         self.nearPlane, self.farPlane = 0.1, 1000.0
 
@@ -506,7 +513,7 @@ class PySceneBuilder:
         self._B = builder or ingest.SceneBuilder()
         self._mat_ids: dict[int, int] = {}       # id(StandardMaterial) -> material index
         self._materials: list[StandardMaterial] = []
-        self._nodes: list[tuple[np.ndarray, int]] = []  # (local matrix, parent)
+        self._nodes = self._B.nodes  # (local matrix, parent): the builder's scene graph
         self._cameras: list[Camera] = []
         self.envMap = None
         self.settings = _Inert()
@@ -562,13 +569,12 @@ class PySceneBuilder:
     def addNode(self, name, transform: Transform | None = None, parent=INVALID_ID) -> int:
         if parent != INVALID_ID and not 0 <= parent < len(self._nodes):
             raise ValueError(f"addNode: parent {parent} does not exist")
-        self._nodes.append(((transform or Transform()).matrix, parent))
-        return len(self._nodes) - 1
+        return self._B.add_node((transform or Transform()).matrix, parent)
 
     def addMeshInstance(self, nodeID, meshID):
         if not 0 <= nodeID < len(self._nodes) or not 0 <= meshID < len(self._B.meshes):
             raise ValueError("addMeshInstance: invalid node or mesh id")
-        self._B.add_instance(meshID, self._world(nodeID))  # in call order, like importScene's
+        self._B.add_instance(meshID, self._world(nodeID), node=nodeID)  # in call order, like importScene's
 
     def _world(self, node) -> np.ndarray:
         M, parent = self._nodes[node]
@@ -608,11 +614,30 @@ class PySceneBuilder:
 
     getVolume = getGridVolume
 
-    def addAnimation(self, animation):
-        pass
+    def addAnimation(self, animation: Animation):
+        """SceneBuilder::addAnimation: the animation drives its node (and what hangs below it) from now on."""
+        if not isinstance(animation, Animation):
+            raise ValueError("addAnimation: 'animation' is missing")
+        if not 0 <= animation.nodeID < len(self._nodes):
+            raise ValueError(f"addAnimation: node {animation.nodeID} does not exist")
+        self._B.animations.append(animation)
 
     def createAnimation(self, animatable, name, duration):
-        return _Inert()
+        """SceneBuilder::createAnimation (:956-976): an animation on the animatable's node, which is created if it
+        has none; None when that node is animated already.  Cameras and lights are the animatables here: their
+        animation is kept but moves no geometry."""
+        if animatable is None:
+            raise ValueError("createAnimation: 'animatable' is missing")
+        node = getattr(animatable, "nodeID", INVALID_ID)
+        node = INVALID_ID if not isinstance(node, int) else node
+        if node != INVALID_ID and any(a.nodeID == node for a in self._B.animations):
+            return None
+        if node == INVALID_ID:
+            node = self.addNode(name)
+        animatable.nodeID = node
+        animation = Animation(name, node, duration)
+        self.addAnimation(animation)
+        return animation
 
     def getSettings(self):
         return self.settings
@@ -630,9 +655,9 @@ def namespace(sb: PySceneBuilder) -> dict:
     ns = dict(sceneBuilder=sb, float2=float2, float3=float3, float4=float4, Transform=Transform,
               CompositionOrder=CompositionOrder, TriangleMesh=TriangleMesh, StandardMaterial=StandardMaterial,
               Material=Material, AlphaMode=AlphaMode, MaterialTextureSlot=MaterialTextureSlot,
-              ShadingModel=ShadingModel, Camera=Camera, NodeID=INVALID_ID)
+              ShadingModel=ShadingModel, Camera=Camera, NodeID=INVALID_ID, Animation=Animation)
     for name in ("EnvMap", "PointLight", "DirectionalLight", "DistantLight", "AnalyticAreaLight", "RectLight",
-                 "DiscLight", "SphereLight", "GridVolume", "Grid", "SDFGrid", "Animation", "HairMaterial",
+                 "DiscLight", "SphereLight", "GridVolume", "Grid", "SDFGrid", "HairMaterial",
                  "ClothMaterial", "MERLMaterial", "PBRTDiffuseMaterial", "PBRTConductorMaterial",
                  "PBRTDielectricMaterial", "RGLMaterial", "SceneBuilderFlags", "Falcor"):
         ns[name] = _inert(name)

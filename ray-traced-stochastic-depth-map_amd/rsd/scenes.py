@@ -81,6 +81,7 @@ class Scene:
     flags: np.ndarray      # uint32 [nt]
     camera: dict           # look-at camera: pos, target, up
     alpha: AlphaMaterials | None = None
+    rig: object | None = None  # rsd.animation.Rig of an animated scene (rsd.ingest.SceneBuilder.build), else None
 
     @property
     def triangle_count(self) -> int:
