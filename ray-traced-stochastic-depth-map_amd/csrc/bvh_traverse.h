@@ -9,15 +9,13 @@
 #include "rsd_device.h"
 #include "../../include/rsd.h"
 #include "alpha_test.h"
+#include "sd_plan.h"  // kTile, kQueueParts, kBlock
 
 namespace rsd {
 
 // __forceinline__ spelled for a lambda's call operator
 #define RSD_INLINE_LAMBDA __attribute__((always_inline))
 
-constexpr int kTile = 8;               // 8x8 texels per wave
-constexpr uint32_t kQueueParts = 32;   // live-ray queue partitions (counter sharding)
-constexpr int kBlock = kTile * kTile;  // 64 threads
 constexpr int kLdsStack = 16;
 constexpr int kStackTotal = 96;        // 4-wide: <= 3 pushes per level, <= 30 levels
 

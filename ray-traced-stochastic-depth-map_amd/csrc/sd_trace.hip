@@ -37,17 +37,7 @@ namespace rsd {
 // ------------------------------------------------------------------------------------
 // SD map kernel
 // ------------------------------------------------------------------------------------
-// queue-control words of one trace: {count[32], head[32]} of the live-ray queue partitions, the
-// raster walk's live-tile count, spare
-constexpr int kQctlWords = 5 * (int)kQueueParts + 32;
-constexpr int kQctlTouch = 4 * (int)kQueueParts + 32;  // two-pass setup: touched texels listed per partition
-constexpr int kQctlHead2 = 3 * (int)kQueueParts + 32;  // hybrid walk: the row walk's own dequeue heads
-constexpr int kQctlLiveTiles = 2 * (int)kQueueParts;
-constexpr int kQctlShort = 2 * (int)kQueueParts + 32;  // lpt: short-ray counts (filled from the partition's end)
-#ifndef RSD_SETUP_WAVES
-#define RSD_SETUP_WAVES 4
-#endif
-constexpr int kSetupWaves = RSD_SETUP_WAVES;  // sd_setup_kernel: tiles (waves) per workgroup (A/B: RSD_SETUP_WAVES)
+// (the queue-control words kQctl*, the workgroup shapes and the other launch-geometry constants: sd_plan.h)
 struct SDArgs {
     const float4* nodes;  // BVH base (wide nodes, then triangle records)
     const float4* tris;   // = nodes + triOff
@@ -354,15 +344,9 @@ __device__ __forceinline__ bool sd_any_hit(const SDArgs& a, float rng, float z, 
 // step lane q tests triangle q.  The 4 child keys are sorted across the quad with
 // __shfl_xor compare-exchanges, the nearest is taken and the rest go to the ray's LDS
 // stack.  Every lane keeps an identical copy of the ray's k-list; accepted hits are
-// broadcast one by one and inserted by all 4 lanes.  A wave walks 16 rays.
+// broadcast one by one and inserted by all 4 lanes.  A wave walks 16 rays (kQuadRays), each with an LDS
+// stack of SDArgs.quadStack entries (quad_stack_entries, sd_plan.h).
 // ------------------------------------------------------------------------------------
-constexpr int kQuadRays = kBlock / 4;   // rays per wave
-// per-ray LDS stack of the quad walks, sized per scene at launch (dynamic LDS, SDArgs.quadStack): a
-// depth-first 4-wide walk holds <= 3 pushed siblings per level below its start, plus the entry items it
-// has not popped yet, so quad_stack_entries(wide depth) entries never overflow.  Sized to the tree, the
-// stack of configs[1]-[4]'s trees (4-wide depth 15-18: 56-64 entries) takes 7-8 KB per wave instead of round 4's fixed 96
-// entries (12 KB), and LDS no longer caps the persistent waves below their register limit (13 per CU).
-constexpr uint32_t quad_stack_entries(uint32_t wideDepth) { return (3u * wideDepth + 7u + 7u) & ~7u; }
 
 // Quad-local exchange through DPP quad_perm (a VALU modifier: no LDS round trip, unlike
 // __shfl / ds_bpermute).  CTRL = quad_perm(p0,p1,p2,p3) = p0 | p1<<2 | p2<<4 | p3<<6.
@@ -872,14 +856,7 @@ __global__ void __launch_bounds__(kSetupWaves * kBlock) sd_setup_kernel(SDArgs a
 // not clean) and lists the touched texels -- rayMin lowered by pass 1 -- per queue partition (one atomic per
 // workgroup); pass B gives every listed texel a lane, densely, for the chain.  Same records, same stores: the
 // bits of the map are the one-pass setup's (a tile with touched but dead texels is stamped unknown instead of
-// clean: it is rewritten once more on its next trace, conservatively).
-constexpr int kClassWaves = 4;   // sd_classify_kernel: waves per workgroup
-#ifndef RSD_CLASS_TILES
-#define RSD_CLASS_TILES 4
-#endif
-constexpr int kClassTiles = RSD_CLASS_TILES;  // sd_classify_kernel: 8x8 tiles per wave (their loads in one round trip)
-constexpr int kLiveBlock = 256;  // sd_live_kernel: lanes per workgroup (4 waves)
-
+// clean: it is rewritten once more on its next trace, conservatively).  (kClassWaves, kClassTiles, kLiveBlock: sd_plan.h)
 template <int N>
 __global__ void __launch_bounds__(kClassWaves * kBlock) sd_classify_kernel(SDArgs a, uint32_t* __restrict__ qctl,
                                                                            uint32_t* __restrict__ qctlNext) {
@@ -999,9 +976,6 @@ __global__ void __launch_bounds__(kClassWaves * kBlock) sd_classify_kernel(SDArg
 // queue partition -- and the static rows of the walk that read it; the wave of 64 listed texels c therefore appends to
 // queue partition (p + c) % kQueueParts (one-pass setup: tile t -> t % kQueueParts), which holds at most
 // touchCap + 2 * 64 * kQueueParts rays (partCap covers that).
-#ifndef RSD_LIVE_WAVES
-#define RSD_LIVE_WAVES 1
-#endif
 template <int N>
 __global__ void __launch_bounds__(kLiveBlock) __attribute__((amdgpu_waves_per_eu(RSD_LIVE_WAVES))) sd_live_kernel(SDArgs a, float4* __restrict__ queue,
                                                              uint32_t* __restrict__ qctl) {
@@ -1315,7 +1289,6 @@ __global__ void __launch_bounds__(kBlock) sd_trace_ordered_kernel(SDArgs a, cons
 // range misses the triangle's are skipped, footprints over kRasterSmall texels are walked by the
 // whole wave.
 // ------------------------------------------------------------------------------------
-constexpr int kRasterBlock = 256;
 constexpr int kRasterSmall = 16;
 
 __device__ __forceinline__ float dot3(const float* a, f3 v) { return a[0] * v.x + a[1] * v.y + a[2] * v.z; }
@@ -1485,10 +1458,9 @@ __global__ void __launch_bounds__(kRasterBlock) sd_raster_kernel(SDArgs a, const
 // K nearest keys -- and the SD texel -- do not depend on the visiting order.
 // Pool bound: a row pops 16 items per step while the pool holds <= poolSoft items and one
 // item (a depth-first step, +3 items per level at most) above, so the pool never exceeds
-// poolSoft + 48 + 3 * (wide tree depth) <= kPoolCap (poolSoft is derived from the depth).
+// poolSoft + 48 + 3 * (wide tree depth) <= kPoolCap (poolSoft is derived from the depth: sd_plan.cpp).
 // A wave walks 4 rays; every row refills from the live-ray queue on its own.
 // ------------------------------------------------------------------------------------
-constexpr int kPoolCap = 256;  // work items per ray (LDS: rays per wave x 256 x 8 B)
 
 template <int ROW>
 __device__ __forceinline__ uint32_t row_bits(bool p, int base) {
@@ -2344,86 +2316,64 @@ __global__ void __launch_bounds__(kBlock) sd_resolve_row_kernel(SDArgs a, const 
 // ------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------
-// walk: 0 = quad (depth-first), 1 = row walk + in-kernel algorithm, 2 = split (row walk ->
-// keys -> resolve kernel), 3 = traversal-order any-hit stream (rsd_hit_order), 4 = raster (triangles
-// -> 64-bit key lists -> resolve kernel)
-static size_t quad_stack_bytes(const SDArgs& a) { return (size_t)a.quadStack * kQuadRays * 8u; }
-
-// RSD_TRACE_SPEC=off: the generic walks (A/B runs)
-static bool specEnvOff() {
-    const char* e = std::getenv("RSD_TRACE_SPEC");
-    return e && std::string(e) == "off";
-}
-
+// The launches of one trace: the setup (one-pass, or classify + live), then the walk the plan chose (SdPlan.walk)
 template <int K, int N>
-static hipError_t launch_sd_kn(const SDArgs& a, dim3 grid, uint32_t persistentBlocks, float4* queue, uint32_t* qctl,
-                               uint2* keys, int walk, int pool, hipStream_t s) {
+static hipError_t launch_sd_kn(const SDArgs& a, const SdPlan& pl, float4* queue, uint32_t* qctl, uint2* keys,
+                               hipStream_t s) {
     constexpr int ROW = K <= 8 ? 8 : 16;
     uint32_t* qctlNext = a.qctlNext;
-    if (a.touchList) {  // the two-pass setup
-        const dim3 cgrid((grid.x + kClassWaves * kClassTiles - 1) / (kClassWaves * kClassTiles), grid.y);
-        hipLaunchKernelGGL((sd_classify_kernel<N>), cgrid, dim3(kClassWaves * kBlock), 0, s, a, qctl, qctlNext);
+    if (pl.twoPass) {
+        hipLaunchKernelGGL((sd_classify_kernel<N>), dim3(pl.classGrid[0], pl.classGrid[1]), dim3(kClassWaves * kBlock), 0, s, a, qctl, qctlNext);
         hipError_t e0 = hipGetLastError();
         if (e0 != hipSuccess) return e0;
-        hipLaunchKernelGGL((sd_live_kernel<N>), dim3(a.liveBlocks), dim3(kLiveBlock), 0, s, a, queue, qctl);
+        hipLaunchKernelGGL((sd_live_kernel<N>), dim3(pl.liveBlocks), dim3(kLiveBlock), 0, s, a, queue, qctl);
     } else {
-        const dim3 sgrid((grid.x + kSetupWaves - 1) / kSetupWaves, grid.y);
-        hipLaunchKernelGGL((sd_setup_kernel<N>), sgrid, dim3(kSetupWaves * kBlock), 0, s, a, queue, qctl, qctlNext);
+        hipLaunchKernelGGL((sd_setup_kernel<N>), dim3(pl.setupGrid[0], pl.setupGrid[1]), dim3(kSetupWaves * kBlock), 0, s, a, queue, qctl, qctlNext);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const dim3 pg(persistentBlocks), wb(kBlock);
-    if (walk == 2) {
-        if (a.counters) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, true, true>), pg, wb, 0, s, a, queue, qctl, keys);
-        else if (pool == 128) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, true, false, 128>), pg, wb, 0, s, a, queue, qctl, keys);
+    const dim3 pg(pl.persistentBlocks), wb(kBlock);
+    const size_t lds = pl.ldsBytes;
+    const bool cnt = pl.counters, small = pl.pool == 128;
+    if (pl.walk == 2) {
+        if (cnt) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, true, true>), pg, wb, 0, s, a, queue, qctl, keys);
+        else if (small) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, true, false, 128>), pg, wb, 0, s, a, queue, qctl, keys);
         else hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, true, false>), pg, wb, 0, s, a, queue, qctl, keys);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL((sd_resolve_row_kernel<K, N, ROW>), pg, wb, 0, s, a, queue, qctl, keys);
-    } else if (walk == 3) {
-        hipLaunchKernelGGL((sd_trace_ordered_kernel<N>), pg, wb, quad_stack_bytes(a), s, a, queue, qctl);
-    } else if (walk == 5) {
+    } else if (pl.walk == 3) {
+        hipLaunchKernelGGL((sd_trace_ordered_kernel<N>), pg, wb, lds, s, a, queue, qctl);
+    } else if (pl.walk == 5) {
         hipLaunchKernelGGL((sd_trace_wavefront_kernel<N>), pg, wb, 0, s, a, queue, qctl);
-    } else if (walk == 6) {
-        // 8-lane rows at every K (K = 16: two keys per lane, row_insert2)
-        const size_t rowLds = (size_t)(kBlock / 8) * pool * 8u, lds = std::max(rowLds, quad_stack_bytes(a));
-        if (pool == 128) hipLaunchKernelGGL((sd_trace_hybrid_kernel<K, N, 8, 128>), pg, wb, lds, s, a, queue, qctl, keys);
+    } else if (pl.walk == 6) {
+        if (small) hipLaunchKernelGGL((sd_trace_hybrid_kernel<K, N, 8, 128>), pg, wb, lds, s, a, queue, qctl, keys);
         else hipLaunchKernelGGL((sd_trace_hybrid_kernel<K, N, 8, kPoolCap>), pg, wb, lds, s, a, queue, qctl, keys);
-    } else if (walk == 4) {
-        hipLaunchKernelGGL((sd_raster_kernel<K>), dim3((a.nTris + kRasterBlock - 1) / kRasterBlock), dim3(kRasterBlock),
-                           0, s, a, queue, qctl);
+    } else if (pl.walk == 4) {
+        hipLaunchKernelGGL((sd_raster_kernel<K>), dim3(pl.rasterBlocks), dim3(kRasterBlock), 0, s, a, queue, qctl);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL((sd_resolve_row_kernel<K, N, ROW, true>), pg, wb, 0, s, a, queue, qctl, keys);
-    } else if (walk == 1) {
-        // the specialised walk (RSD_TRACE_SPEC=off: the generic one, A/B runs)
-        const char* specEnv = std::getenv("RSD_TRACE_SPEC");
-        const bool spec = !(specEnv && std::string(specEnv) == "off") && !a.alphaTest && a.impl != 1u &&
-                          a.impl != 3u && a.maxCount <= (uint32_t)K;
-        if (a.counters) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, false, true>), pg, wb, 0, s, a, queue, qctl, keys);
-        else if (spec && pool == 128) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, false, false, 128, true>), pg, wb, 0, s, a, queue, qctl, keys);
-        else if (spec) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, false, false, kPoolCap, true>), pg, wb, 0, s, a, queue, qctl, keys);
+    } else if (pl.walk == 1) {
+        if (cnt) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, false, true>), pg, wb, 0, s, a, queue, qctl, keys);
+        else if (pl.spec && small) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, false, false, 128, true>), pg, wb, 0, s, a, queue, qctl, keys);
+        else if (pl.spec) hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, false, false, kPoolCap, true>), pg, wb, 0, s, a, queue, qctl, keys);
         else hipLaunchKernelGGL((sd_trace_row_kernel<K, N, ROW, false, false>), pg, wb, 0, s, a, queue, qctl, keys);
     } else {
-        // the specialised quad walk (the row walk's conditions; RSD_TRACE_SPEC=off: the generic one)
-        const char* specEnv = std::getenv("RSD_TRACE_SPEC");
-        const bool spec = !(specEnv && std::string(specEnv) == "off") && !a.alphaTest && a.impl != 1u &&
-                          a.impl != 3u && a.maxCount <= (uint32_t)K && !a.counters;
-        const size_t lds = quad_stack_bytes(a);
-        if (a.counters) hipLaunchKernelGGL((sd_trace_queue_kernel<K, N, false, true>), pg, wb, lds, s, a, queue, qctl);
-        else if (spec) hipLaunchKernelGGL((sd_trace_queue_kernel<K, N, true>), pg, wb, lds, s, a, queue, qctl);
+        if (cnt) hipLaunchKernelGGL((sd_trace_queue_kernel<K, N, false, true>), pg, wb, lds, s, a, queue, qctl);
+        else if (pl.spec) hipLaunchKernelGGL((sd_trace_queue_kernel<K, N, true>), pg, wb, lds, s, a, queue, qctl);
         else hipLaunchKernelGGL((sd_trace_queue_kernel<K, N>), pg, wb, lds, s, a, queue, qctl);
     }
     return hipGetLastError();
 }
 
 template <int K>
-static hipError_t launch_sd_k(const SDArgs& a, uint32_t N, dim3 grid, uint32_t pb, float4* q, uint32_t* qc, uint2* keys,
-                              int walk, int pool, hipStream_t s) {
+static hipError_t launch_sd_k(const SDArgs& a, const SdPlan& pl, uint32_t N, float4* q, uint32_t* qc, uint2* keys,
+                              hipStream_t s) {
     switch (N) {
-        case 1: return launch_sd_kn<K, 1>(a, grid, pb, q, qc, keys, walk, pool, s);
-        case 2: return launch_sd_kn<K, 2>(a, grid, pb, q, qc, keys, walk, pool, s);
-        case 4: return launch_sd_kn<K, 4>(a, grid, pb, q, qc, keys, walk, pool, s);
-        case 8: return launch_sd_kn<K, 8>(a, grid, pb, q, qc, keys, walk, pool, s);
-        case 16: return launch_sd_kn<K, 16>(a, grid, pb, q, qc, keys, walk, pool, s);
+        case 1: return launch_sd_kn<K, 1>(a, pl, q, qc, keys, s);
+        case 2: return launch_sd_kn<K, 2>(a, pl, q, qc, keys, s);
+        case 4: return launch_sd_kn<K, 4>(a, pl, q, qc, keys, s);
+        case 8: return launch_sd_kn<K, 8>(a, pl, q, qc, keys, s);
+        case 16: return launch_sd_kn<K, 16>(a, pl, q, qc, keys, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -2520,75 +2470,51 @@ rsd_status rsd::sd_coverage_lut(int dev, uint32_t N, const int32_t** idx, const 
 namespace {
 // The SD trace of the 8-row tile rows t = start + k * step, k < n (rsd_sd_trace_band_ex: an
 // interleaved band; rsd_sd_trace_rows: a contiguous range).
-rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_params* p, const float* d_linear_z,
-                         uint32_t z_w, uint32_t z_h, uint32_t* d_ray_min, uint32_t* d_ray_max, float* d_sd_out,
-                         uint32_t sd_w, uint32_t sd_h, uint32_t start, uint32_t step, uint32_t n, uint32_t flags,
-                         rsd_counters* counters, rsd_stream stream) {
-    const bool consume = (flags & RSD_SD_CONSUME_INTERVALS) != 0u;
-    const bool throughput = (flags & RSD_SD_THROUGHPUT) != 0u;
-    if (flags & ~(RSD_SD_CONSUME_INTERVALS | RSD_SD_THROUGHPUT)) {
-        set_error("rsd_sd_trace_band_ex: unknown flag");
-        return RSD_ERR_INVALID_ARG;
-    }
-    if (consume && (!p || !p->ray_interval || !d_ray_min || !d_ray_max)) {
-        set_error("rsd_sd_trace_band_ex: RSD_SD_CONSUME_INTERVALS needs RayInterval and both interval maps");
-        return RSD_ERR_INVALID_ARG;
-    }
-    if (!scene || !cam || !p || !d_linear_z || !d_sd_out || sd_w == 0 || sd_h == 0 || z_w == 0 || z_h == 0) {
-        set_error("rsd_sd_trace: null argument or empty extent");
-        return RSD_ERR_INVALID_ARG;
-    }
+//
+// What runs is decided by sd_plan (sd_plan.cpp, host only and tested on the CPU); this function allocates what the
+// plan sized, fills SDArgs from the plan and the scene's device pointers, and launches.
+
+// Grow-only device scratch: a request beyond the capacity drains the stream (its earlier traces may still use the
+// old allocation), then frees and reallocates
+template <class T>
+rsd_status grow_scratch(T*& d, size_t& cap, size_t need, hipStream_t s) {
+    if (cap >= need) return RSD_OK;
+    RSD_HIP(hipStreamSynchronize(s));
+    (void)hipFree(d);
+    d = nullptr;
+    cap = 0;
+    RSD_HIP(hipMalloc(&d, need));
+    cap = need;
+    return RSD_OK;
+}
+
+// A scene without geometry: every texel keeps DEFAULT_DEPTH
+rsd_status sd_trace_empty(const rsd_sd_params* p, uint32_t* d_ray_min, uint32_t* d_ray_max, float* d_sd_out,
+                          uint32_t sd_w, uint32_t sd_h, bool consume, rsd_counters* counters, rsd_stream stream) {
     const uint32_t N = p->sample_count;
-    if (N != 1 && N != 2 && N != 4 && N != 8 && N != 16) {
-        // StochasticDepthMapRT.cpp:190 throws for other N; 16 is the documented extension
-        set_error("rsd_sd_trace: SampleCount must be 1, 2, 4, 8 or 16");
-        return RSD_ERR_UNSUPPORTED;
+    const float def = p->normalize ? 1.0f : 3.40282347e+37f;
+    const size_t n = (size_t)sd_w * sd_h * (N < 4 ? N : 4) * ((N + 3) / 4);
+    std::vector<float> h(n, def);
+    std::vector<uint16_t> h16(n, p->normalize ? (uint16_t)0x3c00u : (uint16_t)0x7c00u);  // 1.0 / +inf
+    if (p->use_16bit)
+        RSD_HIP(hipMemcpyAsync(d_sd_out, h16.data(), n * 2, hipMemcpyHostToDevice, (hipStream_t)stream));
+    else
+        RSD_HIP(hipMemcpyAsync(d_sd_out, h.data(), n * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+    RSD_HIP(hipStreamSynchronize((hipStream_t)stream));
+    if (consume) {
+        rsd_status cs = rsd_svao_clear_intervals(d_ray_min, d_ray_max, sd_w * sd_h, stream);
+        if (cs != RSD_OK) return cs;
     }
-    if (p->implementation == RSD_SD_RESERVOIR_SAMPLING || p->implementation > RSD_SD_KBUFFER) {
-        set_error("rsd_sd_trace: ReservoirSampling is a raster-only implementation");
-        return RSD_ERR_UNSUPPORTED;
-    }
-    if (p->hit_order > RSD_HIT_ORDER_WAVEFRONT) {
-        set_error("rsd_sd_trace: hit_order must be RSD_HIT_ORDER_CANONICAL, _TRAVERSAL or _WAVEFRONT");
-        return RSD_ERR_INVALID_ARG;
-    }
-    if (p->use_16bit && N > 4) {
-        // StochasticDepthMapRT.cpp:199 throws for 16-bit maps with more than 4 samples
-        set_error("rsd_sd_trace: Use16Bit supports SampleCount 1, 2 and 4 only");
-        return RSD_ERR_UNSUPPORTED;
-    }
-    if (p->max_count == 0 && p->implementation != RSD_SD_COVERAGE_MASK) {
-        set_error("rsd_sd_trace: MaxCount must be >= 1");
-        return RSD_ERR_INVALID_ARG;
-    }
-    if (2 * p->guard_band >= (int32_t)sd_w || 2 * p->guard_band >= (int32_t)sd_h || p->guard_band < 0) {
-        set_error("rsd_sd_trace: GuardBand leaves no interior");
-        return RSD_ERR_INVALID_ARG;
-    }
-    if (scene->triangle_count == 0) {
-        // no geometry: every texel keeps DEFAULT_DEPTH
-        const float def = p->normalize ? 1.0f : 3.40282347e+37f;
-        const size_t n = (size_t)sd_w * sd_h * (N < 4 ? N : 4) * ((N + 3) / 4);
-        std::vector<float> h(n, def);
-        std::vector<uint16_t> h16(n, p->normalize ? (uint16_t)0x3c00u : (uint16_t)0x7c00u);  // 1.0 / +inf
-        if (p->use_16bit)
-            RSD_HIP(hipMemcpyAsync(d_sd_out, h16.data(), n * 2, hipMemcpyHostToDevice, (hipStream_t)stream));
-        else
-            RSD_HIP(hipMemcpyAsync(d_sd_out, h.data(), n * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
-        RSD_HIP(hipStreamSynchronize((hipStream_t)stream));
-        if (consume) {
-            rsd_status cs = rsd_svao_clear_intervals(d_ray_min, d_ray_max, sd_w * sd_h, stream);
-            if (cs != RSD_OK) return cs;
-        }
-        if (counters) { *counters = rsd_counters{}; counters->rays_dispatched = (uint64_t)sd_w * sd_h; }
-        return RSD_OK;
-    }
+    if (counters) { *counters = rsd_counters{}; counters->rays_dispatched = (uint64_t)sd_w * sd_h; }
+    return RSD_OK;
+}
+
+// The kernels' arguments that do not point into a workspace: the call's, the scene's and the plan's
+SDArgs sd_args(const rsd_scene* scene, const rsd_camera* cam, const rsd_sd_params* p, const float* d_linear_z,
+               uint32_t z_w, uint32_t z_h, uint32_t* d_ray_min, uint32_t* d_ray_max, float* d_sd_out, uint32_t sd_w,
+               uint32_t sd_h, uint32_t start, uint32_t step, uint32_t n, bool consume, const SdPlan& pl) {
     SDArgs a{};
     a.nodes = scene->d_nodes;
-    {
-        const char* pEnv = std::getenv("RSD_TRACE_PRIO");  // A/B runs: the trace's waves ahead of other frames' passes
-        a.prio = pEnv && std::string(pEnv) == "on" ? 1u : 0u;
-    }
     a.tris = scene->d_tris;
     a.triOff = scene->tri_offset;
     a.cam = *cam;
@@ -2608,57 +2534,46 @@ rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_p
     a.rayInterval = p->ray_interval;
     a.cull = p->cull_mode;
     a.alpha = p->alpha;
-    a.lutIdx = nullptr;
-    a.lut = nullptr;
-    a.counters = nullptr;
+    a.partCap = pl.partCap;
     a.bandStart = (int)start;
     a.bandStep = (int)step;
     a.bandN = (int)n;
-    a.alphaTest = p->alpha_test && scene->d_alpha ? 1u : 0u;
-    a.f16 = p->use_16bit ? 1u : 0u;
-    a.deadFast = 0u;
+    a.poolSoft = pl.poolSoft;
+    a.deadFast = pl.deadFast;
     a.consume = consume ? 1u : 0u;
     a.rayMinW = d_ray_min;
     a.rayMaxW = d_ray_max;
-    // Lower bound of dot(normalize(W), normalize(cam_dir)) over every texel centre of the map
-    // (guard band included, +-1 texel): the cosine of every SD ray's direction to the view axis
-    double cosLower = 0.0;
-    {
-        const int dimx = (int)sd_w - 2 * p->guard_band, dimy = (int)sd_h - 2 * p->guard_band;
-        auto ndcMax = [](double lo, double hi) { return std::max(std::fabs(2.0 * lo - 1.0), std::fabs(2.0 * hi - 1.0)); };
-        const double nx = ndcMax((-p->guard_band + 0.5) / dimx - cam->jitterX - 1.0 / dimx,
-                                 ((int)sd_w - p->guard_band) / (double)dimx - cam->jitterX + 1.0 / dimx);
-        const double ny = ndcMax((-p->guard_band + 0.5) / dimy + cam->jitterY - 1.0 / dimy,
-                                 ((int)sd_h - p->guard_band) / (double)dimy + cam->jitterY + 1.0 / dimy);
-        auto len = [](const float* v) { return std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); };
-        const double lw = len(cam->W);
-        auto dotw = [&](const float* v) { return ((double)v[0] * cam->W[0] + (double)v[1] * cam->W[1] + (double)v[2] * cam->W[2]) / lw; };
-        const double num = dotw(cam->W) - nx * std::fabs(dotw(cam->U)) - ny * std::fabs(dotw(cam->V));
-        const double den = nx * len(cam->U) + ny * len(cam->V) + lw;
-        if (dimx > 0 && dimy > 0 && den > 0.0) cosLower = num / den;
-    }
-    // if farZ / bound is far below FLT_MAX, TMax < FLT_MAX for every texel, so rayMin ==
-    // asuint(FLT_MAX) means TMin >= FLT_MAX > TMax (dead)
-    if (p->ray_interval && d_ray_min && cosLower > 1e-3 && (double)cam->farZ / (0.5 * cosLower) < 1e37)
-        a.deadFast = 1u;
-    a.raster = 0u;
-    a.lpt = 0u;
-    a.lptLen = 0.0f;
-    {
-        // RSD_TRACE_SPREAD=on: the static first rays dealt row-major over the waves (SDArgs.spread; A/B)
-        const char* spreadEnv = std::getenv("RSD_TRACE_SPREAD");
-        a.spread = spreadEnv && std::string(spreadEnv) == "on" ? 1u : 0u;
-        const char* qrEnv = std::getenv("RSD_TRACE_QRANGE");
-        a.qrange = qrEnv && std::string(qrEnv) == "long" ? 1u : qrEnv && std::string(qrEnv) == "short" ? 2u : 0u;
-        const char* dgEnv = std::getenv("RSD_SETUP_DIAG");  // diagnostics: skip / nolive (results wrong by design)
-        a.diag = dgEnv && std::string(dgEnv) == "skip" ? 1u : dgEnv && std::string(dgEnv) == "nolive" ? 2u : 0u;
-    }
-    // clean tiles: the stamp names what DEFAULT_DEPTH looks like in this map (value, storage, layers)
-    a.tileState = p->d_tile_state;
-    a.tileSig = 1u | (p->normalize ? 2u : 0u) | (p->use_16bit ? 4u : 0u) | ((uint32_t)N << 3);
-    a.tileCount = ((sd_w + kTile - 1) / kTile) * ((sd_h + kTile - 1) / kTile);
+    a.alphaTest = p->alpha_test && scene->d_alpha ? 1u : 0u;
+    a.alphaData = scene->alpha;
+    a.alphaData.spread = rsd_ray_cone_spread(cam->focalLength, sd_h);  // default texture dims = SD map
+    a.f16 = p->use_16bit ? 1u : 0u;
     a.primRec = scene->d_prim_rec;
-    a.entOn = 0u;
+    if (pl.walk == 4) {
+        a.raster = 1u;
+        a.keysK = pl.K;
+        a.nTris = scene->triangle_count;
+        a.tilesW = pl.tilesW;
+        for (int k = 0; k < 3; ++k) {
+            a.projU[k] = pl.projU[k];
+            a.projV[k] = pl.projV[k];
+            a.projW[k] = pl.projW[k];
+            a.camWn[k] = pl.camWn[k];
+        }
+        a.wClip = pl.wClip;
+    }
+    a.lpt = pl.lpt;
+    a.lptLen = pl.lptLen;
+    a.spread = pl.spread;
+    a.quadStack = pl.quadStack;
+    a.qrange = pl.qrange;
+    a.hybridRowBlocks = pl.hybridRowBlocks;
+    a.liveBlocks = pl.liveBlocks;
+    a.rowPrio = pl.rowPrio;
+    a.prio = pl.prio;
+    a.tileState = p->d_tile_state;
+    a.tileSig = pl.tileSig;
+    a.tileCount = pl.tileCount;
+    a.entOn = pl.entOn;
     // a dynamic scene whose geometry moved since the grid was built passes no table: its cells' frontiers need
     // not cover the triangles that moved into them (rsd_scene_rebuild_entry_grid makes it current again)
     const void* const entry = scene->entry_stale ? nullptr : scene->d_entry;
@@ -2670,13 +2585,101 @@ rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_p
     a.entRmax = (int)scene->entry_rmax;
     for (int k = 0; k < 3; ++k) a.entOrigin[k] = scene->entry_origin[k];
     a.entExtent = scene->entry_extent;
-    a.entQ = nullptr;
-    a.rayLog = nullptr;
-    a.alphaData = scene->alpha;
-    a.alphaData.spread = rsd_ray_cone_spread(cam->focalLength, sd_h);  // default texture dims = SD map
+    a.diag = pl.diag;
+    return a;
+}
+
+// The counters of an instrumented trace (and its diagnostics: RSD_TRACE_PHASES, RSD_TRACE_RAYLOG)
+rsd_status sd_read_counters(const SdWorkspace* ws, const SdPlan& pl, const SdKnobs& knobs, uint32_t* rayLog,
+                            rsd_counters* counters, hipStream_t s) {
+    unsigned long long h[32];
+    RSD_HIP(hipMemcpyAsync(h, ws->counters, sizeof(h), hipMemcpyDeviceToHost, s));
+    RSD_HIP(hipStreamSynchronize(s));
+    counters->rays_dispatched = h[0];
+    counters->rays_active = h[1];
+    counters->nodes_visited = h[2];
+    counters->tris_tested = h[3];
+    counters->hits_delivered = h[4];
+    counters->max_nodes_per_ray = h[5];
+    counters->max_steps_per_ray = h[6];
+    counters->sum_ray_clocks = h[7];
+    counters->max_ray_clocks = h[8];
+    counters->leaves_visited = h[9];
+    // walk: the hybrid an uninstrumented trace of this call takes (the kernels a caller's timed traces ran);
+    // walk_instrumented: the walk this instrumented launch ran (its step clocks), never the hybrid
+    counters->walk = (uint64_t)pl.walkReported;
+    counters->walk_instrumented = (uint64_t)pl.walk;
+    counters->entry_lookups = h[19];
+    counters->entry_items = h[20];
+    // row walk (instrumented): per-step clock sums and the clock of the instrumented launch
+    counters->step_fetch_clocks = h[16];
+    counters->step_compute_clocks = h[17];
+    counters->step_pool_clocks = h[18];
+    counters->row_steps = h[14];
+    counters->texels_clean = h[25];
+    counters->shader_clock_mhz = h[22] ? (double)h[21] / ((double)h[22] * 0.01) : 0.0;  // 100 MHz realtime
+    if (knobs.phases)
+        std::fprintf(stderr, "[rsd] row walk phase clocks: fetch %llu step %llu resolve %llu steps %llu loops %llu"
+                     " | step split: mem %llu compute %llu pool %llu | compute split: box+sort %llu"
+                     " tri-tests %llu merge+push %llu\n",
+                     h[11], h[12], h[13], h[14], h[15], h[16], h[17], h[18], h[23], h[24], h[17] - h[23] - h[24]);
+    if (rayLog) {
+        std::vector<uint32_t> lg(pl.rayLogBytes / 4);
+        RSD_HIP(hipMemcpy(lg.data(), rayLog, pl.rayLogBytes, hipMemcpyDeviceToHost));
+        (void)hipFree(rayLog);
+        if (FILE* f = std::fopen(knobs.rayLog.c_str(), "wb")) {
+            std::fwrite(lg.data(), 4, lg.size(), f);
+            std::fclose(f);
+        }
+    }
+    if (h[10]) {  // the pool bound was violated: results of this trace are not reliable
+        set_error("rsd_sd_trace: traversal pool overflow (BVH deeper than the row walk supports)");
+        return RSD_ERR_HIP;
+    }
+    return RSD_OK;
+}
+
+rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_params* p, const float* d_linear_z,
+                         uint32_t z_w, uint32_t z_h, uint32_t* d_ray_min, uint32_t* d_ray_max, float* d_sd_out,
+                         uint32_t sd_w, uint32_t sd_h, uint32_t start, uint32_t step, uint32_t n, uint32_t flags,
+                         rsd_counters* counters, rsd_stream stream) {
+    const SdKnobs knobs = sd_knobs_from_env();  // read per call: tests and A/B runs set them between traces
+    SdPlanIn in;
+    in.nullArg = !scene || !cam || !p || !d_linear_z || !d_sd_out;
+    in.sdW = sd_w; in.sdH = sd_h; in.zW = z_w; in.zH = z_h;
+    in.start = start; in.step = step; in.n = n;
+    in.flags = flags;
+    in.rayMin = d_ray_min != nullptr;
+    in.rayMax = d_ray_max != nullptr;
+    in.counters = counters != nullptr;
+    if (p) in.params = *p;
+    if (cam) in.cam = *cam;
+    if (scene) {
+        in.cuCount = scene->dev->cu_count;
+        in.wideDepth = scene->stats.wide_depth;
+        in.entryTable = scene->d_entry && !scene->entry_stale;
+        in.primRec = scene->d_prim_rec != nullptr;
+        in.alphaData = scene->d_alpha != nullptr;
+        in.triangleCount = scene->triangle_count;
+    }
+    SdPlan pl;
+    std::string err;
+    const rsd_status planned = sd_plan(in, knobs, &pl, &err);
+    if (planned != RSD_OK) {
+        set_error(err);
+        return planned;
+    }
+    if (pl.buildKey != kPlanBuildKey) {
+        set_error("rsd_sd_trace: sd_plan.cpp and sd_trace.hip were built with different RSD_SETUP_WAVES / RSD_CLASS_TILES / RSD_LIVE_WAVES");
+        return RSD_ERR_UNSUPPORTED;
+    }
+    const bool consume = (flags & RSD_SD_CONSUME_INTERVALS) != 0u;
+    if (pl.empty) return sd_trace_empty(p, d_ray_min, d_ray_max, d_sd_out, sd_w, sd_h, consume, counters, stream);
+    SDArgs a = sd_args(scene, cam, p, d_linear_z, z_w, z_h, d_ray_min, d_ray_max, d_sd_out, sd_w, sd_h, start, step, n,
+                       consume, pl);
     if (p->implementation == RSD_SD_COVERAGE_MASK) {
-        rsd_status s = ensure_lut(scene->dev->hip_device, N, &a.lutIdx, &a.lut);
-        if (s != RSD_OK) return s;
+        rsd_status ls = ensure_lut(scene->dev->hip_device, p->sample_count, &a.lutIdx, &a.lut);
+        if (ls != RSD_OK) return ls;
     }
     hipStream_t s = (hipStream_t)stream;
     SdWorkspace* ws = nullptr;
@@ -2689,18 +2692,12 @@ rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_p
         RayTabCache& rt = ws->raytab;
         const RayTabCache key{(int)sd_w, (int)sd_h, p->guard_band, p->jitter, cam->jitterX, cam->jitterY,
                               {cam->W[0], cam->W[1], cam->W[2]}, scene->dev->hip_device};
-        const size_t need = (6 * (size_t)sd_w + 6 * (size_t)sd_h + 3) * sizeof(float);
-        if (!rt.same(key) || rt.cap < need) {
-            if (rt.cap < need) {
-                RSD_HIP(hipStreamSynchronize(s));
-                (void)hipFree(rt.d);
-                rt.d = nullptr;
-                rt.cap = 0;
-                RSD_HIP(hipMalloc(&rt.d, need));
-                rt.cap = need;
-            }
-            const int n = (int)std::max(sd_w, sd_h);
-            hipLaunchKernelGGL(ray_table_kernel, dim3((n + 255) / 256), dim3(256), 0, s, rt.d, (int)sd_w, (int)sd_h,
+        const bool grows = rt.cap < pl.rayTabBytes;
+        rsd_status st = grow_scratch(rt.d, rt.cap, pl.rayTabBytes, s);
+        if (st != RSD_OK) return st;
+        if (grows || !rt.same(key)) {
+            const int m = (int)std::max(sd_w, sd_h);
+            hipLaunchKernelGGL(ray_table_kernel, dim3((m + 255) / 256), dim3(256), 0, s, rt.d, (int)sd_w, (int)sd_h,
                                p->guard_band, p->jitter, cam->jitterX, cam->jitterY, f3{cam->W[0], cam->W[1], cam->W[2]});
             hipError_t te = hipGetLastError();
             if (te != hipSuccess) return hip_fail(te, "ray_table_kernel launch");
@@ -2713,44 +2710,22 @@ rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_p
         RSD_HIP(hipMemsetAsync(ws->counters, 0, 32 * sizeof(unsigned long long), s));
         a.counters = ws->counters;
     }
-    const char* rayLogPath = counters ? std::getenv("RSD_TRACE_RAYLOG") : nullptr;  // diagnostics only
-    const uint32_t tiles = (sd_h + kTile - 1) / kTile;
-    dim3 grid((sd_w + kTile - 1) / kTile, consume ? tiles : n);
-    // k = the MAX_COUNT nearest keys decide Default and KBuffer; coverage mask streams chunks
-    const uint32_t need = p->implementation == RSD_SD_COVERAGE_MASK ? 8u : p->max_count;
-    const uint32_t setupBlocks = grid.x * grid.y;
-    a.partCap = (setupBlocks + kQueueParts - 1) / kQueueParts * (uint32_t)kBlock;
-    // the two-pass setup's touched-texel lists: a partition holds the texels of its classify workgroups (and its
-    // queue partition those texels' rays: partCap covers both)
-    constexpr uint32_t kClassTilesPerBlock = kClassWaves * kClassTiles;
-    const uint32_t classBlocks = (grid.x + kClassTilesPerBlock - 1) / kClassTilesPerBlock * grid.y;
-    const uint32_t touchCap = (classBlocks + kQueueParts - 1) / kQueueParts * (kClassTilesPerBlock * (uint32_t)kBlock);
-    a.partCap = std::max(a.partCap, touchCap + 2u * (uint32_t)kBlock * kQueueParts);
-    // live-ray queue workspace (grow-only; the first call of a larger map allocates)
-    const size_t need_q = std::max(((size_t)(sd_w + kTile - 1) / kTile * ((sd_h + kTile - 1) / kTile) + kQueueParts) * kBlock,
-                                   (size_t)a.partCap * kQueueParts);
-    const uint32_t K = need <= 4 ? 4u : (need <= 8 ? 8u : 16u);
-    // split walk (trace -> keys -> resolve) when one chunk of K keys decides every texel
-    const bool split = p->implementation != RSD_SD_COVERAGE_MASK && p->max_count <= K;
-    const size_t queueBytes = need_q * 32, keyBytes = split ? need_q * K * sizeof(uint2) : 0;
-    const size_t entBytes = entry ? need_q * kEntryCap * sizeof(uint32_t) : 0;
-    const size_t touchBytes = (size_t)touchCap * kQueueParts * sizeof(uint32_t);
-    if (ws->queue_cap < queueBytes + keyBytes + entBytes + touchBytes) {
-        RSD_HIP(hipStreamSynchronize(s));
-        (void)hipFree(ws->queue);
-        ws->queue = nullptr;
-        ws->queue_cap = 0;
-        RSD_HIP(hipMalloc(&ws->queue, queueBytes + keyBytes + entBytes + touchBytes));
-        ws->queue_cap = queueBytes + keyBytes + entBytes + touchBytes;
+    // the live-ray workspace, in the plan's sections
+    {
+        rsd_status st = grow_scratch(ws->queue, ws->queue_cap, pl.workspaceBytes, s);
+        if (st != RSD_OK) return st;
     }
-    uint32_t* touchList = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws->queue) + queueBytes + keyBytes + entBytes);
-    float4* queue = reinterpret_cast<float4*>(ws->queue);
-    uint2* keys = reinterpret_cast<uint2*>(reinterpret_cast<char*>(ws->queue) + queueBytes);
-    if (entBytes) a.entQ = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws->queue) + queueBytes + keyBytes);
-    const size_t rayLogBytes = rayLogPath && *rayLogPath ? need_q * 8 * sizeof(uint32_t) : 0;
-    if (rayLogBytes) {
-        RSD_HIP(hipMalloc(&a.rayLog, rayLogBytes));
-        RSD_HIP(hipMemsetAsync(a.rayLog, 0, rayLogBytes, s));
+    char* const base = static_cast<char*>(ws->queue);
+    float4* queue = reinterpret_cast<float4*>(base);
+    uint2* keys = reinterpret_cast<uint2*>(base + pl.keysOff);
+    if (pl.entBytes) a.entQ = reinterpret_cast<uint32_t*>(base + pl.entOff);
+    if (pl.twoPass) {
+        a.touchList = reinterpret_cast<uint32_t*>(base + pl.touchOff);
+        a.touchCap = pl.touchCap;
+    }
+    if (pl.rayLogBytes) {
+        RSD_HIP(hipMalloc(&a.rayLog, pl.rayLogBytes));
+        RSD_HIP(hipMemsetAsync(a.rayLog, 0, pl.rayLogBytes, s));
     }
     // double-buffered queue control (sd_setup_kernel); both buffers are reset on first use and
     // after a failed launch sequence
@@ -2760,225 +2735,26 @@ rsd_status sd_trace_impl(rsd_scene* scene, const rsd_camera* cam, const rsd_sd_p
     }
     uint32_t* qctl = ws->qctl + (ws->qctl_gen & 1u) * kQctlWords;
     a.qctlNext = ws->qctl + ((ws->qctl_gen + 1u) & 1u) * kQctlWords;
-    // traversal walk: row-parallel (default) unless the tree is too deep for its LDS pool
-    // bound (kPoolCap >= poolSoft + 48 + 3 * depth), or RSD_TRACE_WALK=quad asks for the
-    // depth-first quad walk (A/B measurements)
-    const int depth = (int)std::max(1u, scene->stats.wide_depth);
-    a.quadStack = quad_stack_entries((uint32_t)depth);
-    // the row walk's LDS pool: 128 entries per ray (8 KB per wave) wherever the tree depth allows it
-    // (the pool bound above), else 256; with the specialised walk the smaller pool measured faster alone
-    // (75.7 vs 78.3 us at configs[1]) and leaves more LDS to the other frames' passes
-    // (profiles/round3/ab/trace_pool/).  RSD_TRACE_POOL=256 forces the large pool (A/B runs); the
-    // instrumented (counters) walk always uses 256.
-    static const char* poolEnv = std::getenv("RSD_TRACE_POOL");
-    // (the wavefront stream's order depends on the pool bound: always the 256-entry pool, soft bound below)
-    int pool = (poolEnv && std::atoi(poolEnv) == 256) || counters || p->hit_order == RSD_HIT_ORDER_WAVEFRONT
-                   ? kPoolCap : 128;
-    if (pool - 48 - 3 * depth < 16) pool = kPoolCap;
-    a.poolSoft = std::min(pool - 48 - 3 * depth, 160);
-    const char* walkEnv = std::getenv("RSD_TRACE_WALK");  // read per call: tests cover every walk
-    const std::string walkName = walkEnv ? walkEnv : "";
-    // The row walk wins when few rays are live (the launch is the slowest ray's chain); with
-    // more SD texels the live rays fill the machine and the quad walk's lane utilisation wins
-    // (rsd_sd_trace, row vs quad: 1080p/4 0.43 M texels 92 vs 133 us; 4K/4 1.0 M texels 443 vs
-    // 327 us; 1080p full 6.9 M texels 688 vs 294 us -- DESIGN.md section 4)
-    const uint64_t bandTexels = (uint64_t)sd_w * std::min<uint64_t>((uint64_t)n * kTile, sd_h);
-    // RSD_SD_THROUGHPUT (frames in flight) no longer changes the walk: round 1 measured the quad walk
-    // ahead with frames in flight (108 vs 118 us per frame), but with the segment entry grid and the
-    // longest-first queue the row walk is ahead at every F (20-frame bench, configs[1]: F = 2/3/4/6
-    // -> 169/157/154/161 vs 200/172/162/171 us; profiles/round3/ab/walk_*.json)
-    (void)throughput;
-    const bool rowWalk = a.poolSoft >= 16 && walkName != "quad" &&
-                         (walkName == "fused" || walkName == "split" || bandTexels <= 600000u);
-    // default: the fused row walk; RSD_TRACE_WALK=split|quad for A/B runs
-    // raster walk: triangles -> per-texel K nearest keys (split-eligible canonical traces; the near
-    // clip needs the cosine bound)
-    const bool rasterOk = split && p->hit_order == RSD_HIT_ORDER_CANONICAL && cosLower > 1e-3 && scene->d_prim_rec;
-    const bool raster = rasterOk && walkName == "raster";
-    // the fused row walk carries every key's hit terms from its leaf test, so it needs no resolve
-    // pass; RSD_TRACE_WALK=split keeps the key-list + resolve-kernel variant for A/B runs
-    if (p->hit_order == RSD_HIT_ORDER_WAVEFRONT && a.poolSoft < 16) {
-        set_error("rsd_sd_trace: the BVH is too deep for the wavefront order's LDS pool");
-        return RSD_ERR_UNSUPPORTED;
+    if (pl.walk == 4) {
+        rsd_status st = grow_scratch(ws->raster, ws->raster_cap, pl.rasterBytes, s);
+        if (st != RSD_OK) return st;
+        char* const rbase = static_cast<char*>(ws->raster);
+        a.keys64 = reinterpret_cast<unsigned long long*>(rbase);
+        a.slotMap = reinterpret_cast<int32_t*>(rbase + pl.slotOff);
+        a.tileRec = reinterpret_cast<float2*>(rbase + pl.tileRecOff);
+        a.liveTiles = reinterpret_cast<uint32_t*>(rbase + pl.liveTilesOff);
     }
-    int walk = p->hit_order == RSD_HIT_ORDER_TRAVERSAL ? 3 : p->hit_order == RSD_HIT_ORDER_WAVEFRONT ? 5
-                     : raster ? 4 : !rowWalk ? 0
-                     : (split && walkName == "split") ? 2 : 1;
-    // segment entry grid: canonical walks (row, quad, split) start from the frontier of each ray's
-    // segment; RSD_TRACE_ENTRY=off walks every ray from the root (A/B runs)
-    if ((walk == 0 || walk == 1 || walk == 2) && a.entQ) {
-        const char* entEnv = std::getenv("RSD_TRACE_ENTRY");
-        a.entOn = entEnv && std::string(entEnv) == "off" ? 0u : 1u;
-    }
-    if (walk == 1 || walk == 0 || walk == 5) {
-        // longest-first queue: rays whose interval exceeds 0.1 x TMin are dequeued first (configs[1]:
-        // 90 -> 84 us); RSD_TRACE_LPT = off | a threshold (> 0 absolute, < 0 relative to TMin).  (The
-        // traversal-order walk reads the split queue too, but measured no gain from it: 150.7 vs 147.3 us at
-        // configs[1], profiles/round5/trace_ab/lpt_ordered_c1.json -- its rays start at the root.)
-        const char* lptEnv = std::getenv("RSD_TRACE_LPT");
-        const bool off = lptEnv && std::string(lptEnv) == "off";
-        a.lpt = off ? 0u : 1u;
-        a.lptLen = lptEnv && *lptEnv && !off ? (float)std::atof(lptEnv) : -0.1f;
-    }
-    // two-pass setup (sd_classify_kernel + sd_live_kernel) for the full-resolution maps, where the one-pass setup's
-    // live-ray chains pass through the machine in tens of rounds: configs[2] setup 66 -> 45 us, trace 177 -> 154 us;
-    // configs[4] 202 -> 152 us, 551 -> 487 us at the static pose, 0.989 -> 0.922 ms along the orbit
-    // (profiles/round6/setup_twopass/).  The 1/4-resolution maps keep the one-pass setup: configs[1] 67 -> 72 us (one
-    // round of the chain there: the second launch costs more than it saves), configs[3] (1.0 M texels) 197 -> 215 us
-    // (the setup flat, the hybrid walk slower with the listed order of its rays).  Above 2 M texels;
-    // RSD_SETUP_TWOPASS = on | off overrides (A/B runs, tests of small maps).
-    {
-        const char* tpEnv = std::getenv("RSD_SETUP_TWOPASS");
-        const bool force = tpEnv && std::string(tpEnv) == "on", never = tpEnv && std::string(tpEnv) == "off";
-        if (a.deadFast && walk != 4 && a.diag == 0u && !never && (force || bandTexels > 2000000u)) {
-            a.touchList = touchList;
-            a.touchCap = touchCap;
-            // the resident grid: 5 workgroups of 4 waves per CU (92-94 VGPRs: 5 waves per SIMD), rounded to the partitions
-            const uint32_t perCu = RSD_LIVE_WAVES > 5 ? (uint32_t)RSD_LIVE_WAVES : 5u;
-            a.liveBlocks = ((uint32_t)std::max(1, scene->dev->cu_count) * perCu + kQueueParts - 1) / kQueueParts * kQueueParts;
+    if (pl.launch) {
+        const hipError_t e = pl.K == 4   ? launch_sd_k<4>(a, pl, p->sample_count, queue, qctl, keys, s)
+                             : pl.K == 8 ? launch_sd_k<8>(a, pl, p->sample_count, queue, qctl, keys, s)
+                                         : launch_sd_k<16>(a, pl, p->sample_count, queue, qctl, keys, s);
+        if (e != hipSuccess) {
+            ws->qctl_dirty = true;
+            return hip_fail(e, "sd_trace_kernel launch");
         }
+        ws->qctl_gen++;
     }
-    if (walk == 4) {
-        const uint32_t tilesW = (sd_w + kTile - 1) / kTile, tilesH = (sd_h + kTile - 1) / kTile;
-        const size_t slotBytes = (size_t)sd_w * sd_h * 4, tileBytes = (size_t)tilesW * tilesH * 8;
-        const size_t keys64Bytes = (size_t)a.partCap * kQueueParts * K * 8;
-        const size_t liveBytes = (size_t)tilesW * tilesH * 4;
-        const size_t rb = slotBytes + tileBytes + liveBytes + keys64Bytes + 256;
-        if (ws->raster_cap < rb) {
-            RSD_HIP(hipStreamSynchronize(s));
-            (void)hipFree(ws->raster);
-            ws->raster = nullptr;
-            ws->raster_cap = 0;
-            RSD_HIP(hipMalloc(&ws->raster, rb));
-            ws->raster_cap = rb;
-        }
-        char* base = static_cast<char*>(ws->raster);
-        a.raster = 1u;
-        a.keysK = K;
-        a.nTris = scene->triangle_count;
-        a.keys64 = reinterpret_cast<unsigned long long*>(base);
-        a.slotMap = reinterpret_cast<int32_t*>(base + keys64Bytes);
-        a.tileRec = reinterpret_cast<float2*>(base + keys64Bytes + slotBytes);
-        a.liveTiles = reinterpret_cast<uint32_t*>(base + keys64Bytes + slotBytes + tileBytes);
-        a.primRec = scene->d_prim_rec;
-        a.tilesW = (int)tilesW;
-        auto dot3h = [](const float* u, const float* v) { return (double)u[0] * v[0] + (double)u[1] * v[1] + (double)u[2] * v[2]; };
-        const double uu = dot3h(cam->U, cam->U), vv = dot3h(cam->V, cam->V), ww = dot3h(cam->W, cam->W);
-        for (int k = 0; k < 3; ++k) {
-            a.projU[k] = (float)(cam->U[k] / uu);
-            a.projV[k] = (float)(cam->V[k] / vv);
-            a.projW[k] = (float)(cam->W[k] / ww);
-            a.camWn[k] = (float)(cam->W[k] / std::sqrt(ww));
-        }
-        // every valid hit has t >= TMin >= 0.1 nearZ (initRayDesc eps) and cos >= cosLower, i.e. a
-        // view depth >= 0.1 nearZ cosLower = w |W|: clip at half of that
-        a.wClip = (float)(0.5 * 0.1 * cam->nearZ * cosLower / std::sqrt(ww));
-    }
-    // persistent waves: 8 per CU.  At 1080p/4 every row gets one of the ~22 K live rays in its
-    // static first slot and the launch lasts as long as the slowest ray; 16 waves per CU (the
-    // split walk holds < 128 VGPRs) measured no faster (tools/sd_time.py sweep)
-    // The quad walk keeps its keys distributed over the quad since round 5 (QuadKeys: 177 -> 115 VGPRs at K = 16,
-    // 96 at K = 8), and the full-resolution maps it serves are throughput-bound: 16 waves per CU, the register
-    // limit at K = 16 once its LDS stack is sized to the tree (quad_stack_entries: the fixed 96-entry stack held
-    // residency to 13; configs[4] 827 -> 713 us at 12, 699 -> 671 us from 12 to 16), and at K <= 8 (configs[2]
-    // 263 -> 257 us; 20 measured the same, as did configs[3]); profiles/round5/trace_ab/wpc_*, r5p/.  The row walk
-    // stays at 8 (latency-bound: 10 / 12 / 16 measured no faster).
-    const char* wpcEnv = std::getenv("RSD_TRACE_WAVES_PER_CU");  // experiments only (read per call: A/B runs)
-    const uint32_t wavesPerCu = wpcEnv ? (uint32_t)std::max(1, std::atoi(wpcEnv)) : (walk == 0 ? 16u : 8u);
-    uint32_t pb = ((uint32_t)std::max(1, scene->dev->cu_count) * wavesPerCu + kQueueParts - 1) / kQueueParts *
-                  kQueueParts;
-    // The hybrid walk (round 5): a trace whose longest-first rays -- the ones whose chains set the launch: configs[3]'s
-    // quad walk over them alone is 261 of its 268 us -- take the row walk (8 items per step) in the same launch
-    // (sd_trace_hybrid_kernel: its first blocks run the row walk over the longest-first end of each queue partition,
-    // the others the quad walk over the rest), where the fused row walk (configs[1]: 74 -> 66 us) or the quad walk
-    // (configs[3] 268 -> 195 us, configs[2] 236 -> 177 us) would walk every ray alike.  Only for 8-lane rows
-    // (K <= 8: with K = 16 the 16-lane row walk is the slower one).  With frames in flight (RSD_SD_THROUGHPUT) it
-    // replaces the fused row walk of the small maps (configs[1]: 0.0834-0.0860 -> 0.0815-0.0840 ms per frame, three
-    // alternating pairs, profiles/round6/hybrid_in_flight/), but not the quad walk of the full-resolution maps: there
-    // the machine is already full of other frames' work and the quad walk's lane use wins (RSD_TRACE_HYBRID=all:
-    // configs[2] 0.188-0.191 -> 0.202-0.206 ms per frame, configs[3] 0.308-0.317 -> 0.327-0.347;
-    // profiles/round5/hybrid/in_flight/).  RSD_TRACE_HYBRID=off disables it, =all takes it for every walk;
-    // RSD_TRACE_HYBRID_ROWWPC / RSD_TRACE_WAVES_PER_CU set the row / quad blocks per CU (A/B runs).
-    const char* hyEnv = std::getenv("RSD_TRACE_HYBRID");
-    // K = 16 (round 6, RSD_TRACE_HYBRID16=on; off by default): the row blocks walk 8-lane rows holding two keys per lane
-    // (row_insert2).  Same bits, but slower at configs[4]: 555 -> 688 us static, 0.987 -> 1.597 ms along the orbit
-    // (profiles/round6/hybrid16/).  Its long rays are many (the quad walk over them alone takes 411 of its 547 us: the
-    // set is throughput-bound, where 8 lanes per ray lose to 4), and one launch gives every block the row walk's 191
-    // VGPRs: 8 waves per CU instead of the quad walk's 16 (the quad walk alone at 4 per CU: 972 us).
-    const char* hy16Env = std::getenv("RSD_TRACE_HYBRID16");
-    const bool hybridK = K <= 8 || (hy16Env && std::string(hy16Env) == "on");
-    const bool hybridOk = (walk == 0 || walk == 1) && hybridK && a.lpt && a.poolSoft >= 16 &&
-                          (!throughput || walk == 1 || (hyEnv && std::string(hyEnv) == "all")) &&
-                          !(hyEnv && std::string(hyEnv) == "off") && !a.alphaTest && a.impl != 1u && a.impl != 3u &&
-                          a.maxCount <= (uint32_t)K && !(specEnvOff());
-    if (hybridOk && !counters) {
-        const char* rwEnv = std::getenv("RSD_TRACE_HYBRID_ROWWPC");
-        const uint32_t rw = rwEnv ? (uint32_t)std::max(1, std::atoi(rwEnv)) : 4u, qw = wpcEnv ? wavesPerCu : 8u;
-        const uint32_t cus = (uint32_t)std::max(1, scene->dev->cu_count);
-        a.hybridRowBlocks = (cus * rw + kQueueParts - 1) / kQueueParts * kQueueParts;
-        const char* prEnv = std::getenv("RSD_TRACE_ROWPRIO");
-        a.rowPrio = prEnv && std::string(prEnv) == "on" ? 1u : 0u;
-        pb = a.hybridRowBlocks + (cus * qw + kQueueParts - 1) / kQueueParts * kQueueParts;
-        walk = 6;
-    }
-    hipError_t e = hipSuccess;
-    if (grid.y == 0) {}
-    else if (K == 4) e = launch_sd_k<4>(a, N, grid, pb, queue, qctl, keys, walk, pool, s);
-    else if (K == 8) e = launch_sd_k<8>(a, N, grid, pb, queue, qctl, keys, walk, pool, s);
-    else e = launch_sd_k<16>(a, N, grid, pb, queue, qctl, keys, walk, pool, s);
-    if (e != hipSuccess) {
-        ws->qctl_dirty = true;
-        return hip_fail(e, "sd_trace_kernel launch");
-    }
-    if (grid.y != 0) ws->qctl_gen++;
-    if (counters) {
-        unsigned long long h[32];
-        RSD_HIP(hipMemcpyAsync(h, ws->counters, sizeof(h), hipMemcpyDeviceToHost, s));
-        RSD_HIP(hipStreamSynchronize(s));
-        counters->rays_dispatched = h[0];
-        counters->rays_active = h[1];
-        counters->nodes_visited = h[2];
-        counters->tris_tested = h[3];
-        counters->hits_delivered = h[4];
-        counters->max_nodes_per_ray = h[5];
-        counters->max_steps_per_ray = h[6];
-        counters->sum_ray_clocks = h[7];
-        counters->max_ray_clocks = h[8];
-        counters->leaves_visited = h[9];
-        // walk: the hybrid an uninstrumented trace of this call takes (the kernels a caller's timed traces ran);
-        // walk_instrumented: the walk this instrumented launch ran (its step clocks), never the hybrid
-        counters->walk = (uint64_t)((walk == 0 || walk == 1) && hybridOk ? 6 : walk);
-        counters->walk_instrumented = (uint64_t)walk;
-        counters->entry_lookups = h[19];
-        counters->entry_items = h[20];
-        // row walk (instrumented): per-step clock sums and the clock of the instrumented launch
-        counters->step_fetch_clocks = h[16];
-        counters->step_compute_clocks = h[17];
-        counters->step_pool_clocks = h[18];
-        counters->row_steps = h[14];
-        counters->texels_clean = h[25];
-        counters->shader_clock_mhz = h[22] ? (double)h[21] / ((double)h[22] * 0.01) : 0.0;  // 100 MHz realtime
-        if (const char* dbg = std::getenv("RSD_TRACE_PHASES"))
-            if (*dbg) std::fprintf(stderr, "[rsd] row walk phase clocks: fetch %llu step %llu resolve %llu steps %llu loops %llu"
-                                   " | step split: mem %llu compute %llu pool %llu | compute split: box+sort %llu"
-                                   " tri-tests %llu merge+push %llu\n",
-                                   h[11], h[12], h[13], h[14], h[15], h[16], h[17], h[18], h[23], h[24],
-                                   h[17] - h[23] - h[24]);
-        if (a.rayLog) {
-            std::vector<uint32_t> lg(rayLogBytes / 4);
-            RSD_HIP(hipMemcpy(lg.data(), a.rayLog, rayLogBytes, hipMemcpyDeviceToHost));
-            (void)hipFree(a.rayLog);
-            if (FILE* f = std::fopen(rayLogPath, "wb")) {
-                std::fwrite(lg.data(), 4, lg.size(), f);
-                std::fclose(f);
-            }
-        }
-        if (h[10]) {  // the pool bound was violated: results of this trace are not reliable
-            set_error("rsd_sd_trace: traversal pool overflow (BVH deeper than the row walk supports)");
-            return RSD_ERR_HIP;
-        }
-    }
-    return RSD_OK;
+    return counters ? sd_read_counters(ws, pl, knobs, a.rayLog, counters, s) : RSD_OK;
 }
 
 }  // namespace
