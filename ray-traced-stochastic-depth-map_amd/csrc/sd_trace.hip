@@ -2818,6 +2818,7 @@ void release_sd_workspaces(rsd_scene* scene) {
         (void)hipFree(w->queue);
         (void)hipFree(w->raytab.d);
         (void)hipFree(w->counters);
+        (void)hipFree(w->raster);
         delete w;
     }
     scene->sd_ws.clear();
