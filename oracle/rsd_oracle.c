@@ -1039,7 +1039,7 @@ static int o_any_hit(const osd_params* p, uint32_t N, const int32_t* lutIdx, con
  * librsd DEFINES one: a depth-first walk of its own 4-wide BVH (exported by rsd_scene_export_bvh),
  * children nearest entry distance first, leaf triangles in record order, each triangle once; a
  * committed hit sets TMax = t and later candidates must satisfy t < TMax (RayTCurrent()).  This
- * restates that definition (librsd csrc/sd_trace.hip sd_trace_ordered_ray, box test
+ * restates that definition (librsd csrc/sd_walk_quad.hip sd_trace_ordered_ray, box test
  * csrc/bvh_traverse.h box_hit) over the same tree, so the GPU result is checked bit for bit;
  * the per-hit algorithm is the reference's (o_any_hit). */
 typedef struct { float invd[3], olo[3], ohi[3]; } obox_ray;
@@ -1163,7 +1163,7 @@ static uint64_t o_ordered_walk(const oscene* s, const float* bvh, uint32_t triOf
 }
 
 /* ---- wavefront any-hit stream (rsd.h RSD_HIT_ORDER_WAVEFRONT) -------------------------------
- * The other order librsd defines (librsd csrc/sd_trace.hip sd_trace_wavefront_kernel): the canonical row walk's
+ * The other order librsd defines (librsd csrc/sd_walk_wavefront.hip sd_trace_wavefront_kernel): the canonical row walk's
  * traversal of the exported 4-wide BVH, 8 work items per step.  Per step every held item is tested against the
  * TMax of the step's start (a node's 4 children, sorted by entry distance with the 5-exchange network; a leaf's
  * triangles); the step's candidate hits go to any-hit in lane order, a leaf's triangles in record order, each

@@ -22,7 +22,7 @@ constexpr uint32_t kHaloBlock = 256;
 constexpr uint32_t kFltMaxBits = 0x7f7fffffu;  // asuint(FLT_MAX): a cleared rayMin (SVAO.cpp:339)
 constexpr uint32_t kMaxRegions = 64;
 
-constexpr uint32_t kSdTile = 8;  // SD trace tile rows (sd_trace.hip kTile): the round-robin unit of the tiled split
+constexpr uint32_t kSdTile = 8;  // SD trace tile rows (sd_plan.h kTile): the round-robin unit of the tiled split
 
 struct HaloRegions {
     uint32_t n;

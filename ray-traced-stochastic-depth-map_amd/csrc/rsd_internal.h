@@ -137,7 +137,7 @@ rsd_status refit_enqueue(rsd_scene* s, hipStream_t st);
 // skinning.hip: pose the rig's vertices into the scene's position copy from `d_matrices` (float[matrix_count][12])
 rsd_status pose_enqueue(rsd_scene* s, const float* d_matrices, hipStream_t st);
 
-// sd_trace.hip: the stratified coverage-mask tables of N samples on HIP device `dev` (indices [N + 1], look-up
+// sd_trace.hip (host code): the stratified coverage-mask tables of N samples on HIP device `dev` (indices [N + 1], look-up
 // table [2^N]), uploaded once per (device, N) and never freed; shared by the SD trace and sd_raster.hip
 rsd_status sd_coverage_lut(int dev, uint32_t N, const int32_t** idx, const uint32_t** lut);
 

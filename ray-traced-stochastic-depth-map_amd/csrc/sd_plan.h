@@ -1,7 +1,7 @@
 // sd_plan.h -- the launch plan of one SD trace (host only: no HIP, no device pointers).
 //
 // sd_plan() takes the sizes, parameters and scene facts of one rsd_sd_trace* call and the RSD_TRACE_* /
-// RSD_SETUP_* knobs, and decides everything sd_trace.hip then launches: the walk, K, the LDS pool, the grids, the
+// RSD_SETUP_* knobs, and decides everything sd_trace.hip then launches (through sd_launch.h): the walk, K, the LDS pool, the grids, the
 // setup variant and the layout of the workspaces.  It is a pure function (tests/test_sd_plan.py checks it on the
 // CPU), and this header holds the launch-geometry constants the plan and the kernels must agree on, each defined
 // once.
@@ -40,7 +40,7 @@ constexpr int kLiveBlock = 256;  // sd_live_kernel: lanes per workgroup (4 waves
 #define RSD_LIVE_WAVES 1  // sd_live_kernel: amdgpu_waves_per_eu (A/B)
 #endif
 // the three A/B macros above as one word: sd_plan.cpp records the values it was compiled with (SdPlan.buildKey), and
-// a library whose sd_trace.hip was compiled with others (make variant DEFS=...) refuses to launch
+// a library whose sd_setup.hip was compiled with others (make variant DEFS=...) refuses to launch
 constexpr uint32_t kPlanBuildKey = (uint32_t)RSD_SETUP_WAVES | (uint32_t)RSD_CLASS_TILES << 8 | (uint32_t)RSD_LIVE_WAVES << 16;
 
 constexpr int kQuadRays = kBlock / 4;   // quad walks: rays per wave

@@ -2,7 +2,7 @@
 //
 // A random triangle scene is built with librsd's own host BVH builder and entry-grid builder.  For
 // random ray segments (short and long, inside and outside the scene), the SD setup kernel's lookup
-// (sd_trace.hip entry_lookup, restated here with the same float operations) picks a cell; every
+// (sd_setup.hip entry_lookup, restated here with the same float operations) picks a cell; every
 // triangle the segment clearly crosses (double precision, margins away from edges and interval
 // ends) must lie under one of that cell's frontier items, and a cell reported absent must have no
 // such triangle.  With a spatial-split budget (4th argument, bvh_build.h BvhOptions) the BVH holds
@@ -53,7 +53,7 @@ void collect(const FlatBvh& b, uint32_t triOff, uint32_t item, const Box& box, s
     }
 }
 
-// sd_trace.hip entry_lookup, same float operations; returns -1 dead, 0 root, else slot value
+// sd_setup.hip entry_lookup, same float operations; returns -1 dead, 0 root, else slot value
 int64_t lookup(const EntryGrid& g, V3 o, V3 d, float TMin, float TMax) {
     const float pad = 0x1p-14f * (std::fabs(o.x) + std::fabs(o.y) + std::fabs(o.z) + TMax) + 1e-30f;
     const V3 p0{o.x + d.x * TMin, o.y + d.y * TMin, o.z + d.z * TMin};

@@ -1,4 +1,4 @@
-"""The hybrid SD walk (rsd.h RSD_WALK_HYBRID, csrc/sd_trace.hip walk 6): with one frame in flight the longest-first rays
+"""The hybrid SD walk (rsd.h RSD_WALK_HYBRID, csrc/sd_walk_hybrid.hip walk 6): with one frame in flight the longest-first rays
 take the row walk and the others the quad walk, in one launch (K = 16, an A/B option since round 6: 8-lane rows holding
 two keys per lane).  Canonical hit stream, so the bits must be the single
 walk's (and the oracle's, which the parity / configs tests check at every config)."""

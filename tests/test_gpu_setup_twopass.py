@@ -1,4 +1,4 @@
-"""The two-pass SD setup (csrc/sd_trace.hip sd_classify_kernel + sd_live_kernel, RSD_SETUP_TWOPASS): pass A streams over
+"""The two-pass SD setup (csrc/sd_setup.hip sd_classify_kernel + sd_live_kernel, RSD_SETUP_TWOPASS): pass A streams over
 the map and lists the texels pass 1 touched, pass B evaluates only those.  It is the default for the full-resolution
 maps (configs[2]-[4], whose whole-map parity tests in test_gpu_fullsize.py / test_gpu_configs.py run it); here it is
 forced on small frames and compared with the CPU oracle bit for bit, with the one-pass setup along a camera path with

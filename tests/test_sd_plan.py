@@ -72,7 +72,10 @@ def test_host_only_sources():
     for name in ("sd_plan.h", "sd_plan.cpp"):
         text = (CSRC / name).read_text()
         assert "hip/" not in text and "rsd_internal.h" not in text and "rsd_device.h" not in text, name
-    assert "getenv" not in (CSRC / "sd_trace.hip").read_text()
+    trace = sorted(p for ext in ("h", "hip", "cpp") for p in CSRC.glob(f"sd_*.{ext}") if p.name != "sd_plan.cpp")
+    assert {"sd_trace.hip", "sd_setup.hip", "sd_common.h"} <= {p.name for p in trace}
+    for p in trace:
+        assert "getenv" not in p.read_text(), p.name
 
 
 def test_small_map(exe):

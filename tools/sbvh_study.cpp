@@ -2,7 +2,7 @@
 //
 // Builds librsd's BVH (csrc/bvh_build.cpp) with and without spatial splits plus its segment entry grid
 // (csrc/entry_grid.cpp), and replays the live SD ray segments of a frame (tools/sbvh_rays.py) through a
-// model of the row walk (sd_trace.hip sd_trace_row_kernel): the segment's entry frontier as the first pool,
+// model of the row walk (sd_row.h sd_trace_row_body): the segment's entry frontier as the first pool,
 // then per step up to 8 items popped from the top of the ray's pool, every child box tested against
 // [TMin, min(TMax, k-th key)], the surviving children pushed nearest-on-top lane after lane, leaf hits
 // merged into the K nearest (t, prim) keys (each key once).  Reports the step / node / leaf counts whose
@@ -141,7 +141,7 @@ int main(int argc, char** argv) {
         r.tmin = rays[8 * i + 6];
         r.tmax = rays[8 * i + 7];
         setup(r);
-        // entry lookup (sd_trace.hip entry_lookup)
+        // entry lookup (sd_setup.hip entry_lookup)
         std::vector<uint32_t> pool;
         {
             const float pad = 0x1p-14f * (std::fabs(r.o[0]) + std::fabs(r.o[1]) + std::fabs(r.o[2]) + r.tmax) + 1e-30f;
