@@ -432,3 +432,223 @@ def grade(oracle, r, scene, case, detail=None):
     assert stencil_flip <= DECISION_FRAC, (case, stencil_flip)
     assert touched_flip <= DECISION_FRAC, (case, touched_flip)
     return frame
+
+
+# ---- the CPU rehearsal of the sharded frames (test_sharding.py, test_band_odd.py): the oracle as the backend of
+# rsd.shard.BandFrame / HaloFrame, and a free port for their gloo process groups
+
+class OracleBackend:
+    """BandFrame backend on the CPU oracle; numpy buffers shared with torch tensors."""
+
+    def __init__(self, O, scene, cfg, ss_max_radius=None, whole_config=False):
+        """whole_config: camera, VAOData and the parameter structs from every field of cfg (the odd frames), as
+        tests/test_odd_geometry.py builds them; otherwise the small frames' defaults."""
+        import torch
+        self.O, self.cfg = O, cfg
+        self.osc = O.Scene(scene.positions, scene.indices, scene.flags)
+        W, H = cfg.fb_w, cfg.fb_h
+        aspect = float(np.float32(W) / np.float32(H))
+        N = cfg.sd_samples
+        look = (scene.camera["pos"], scene.camera["target"], scene.camera["up"])
+        if whole_config:
+            from rsd.frame import sd_params, svao_params
+            self.cam = O.camera_look_at(*look, focal_length=cfg.focal_length, frame_height=cfg.frame_height,
+                                        aspect=aspect, near=cfg.near, far=cfg.far)
+            self.vao, self.sd_w, self.sd_h = oracle_vao(O, W, H, cfg.divisor, cfg.sd_guard_px, cfg.radius, cfg.exponent,
+                                                        cfg.thickness)
+            self.sdp = to_oracle(sd_params(cfg, self.vao.sdGuard), O.SDParams)
+            self.svp = to_oracle(svao_params(cfg), O.SVAOParams)
+        else:
+            self.cam = O.camera_look_at(*look, aspect=aspect)
+            self.vao, self.sd_w, self.sd_h = oracle_vao(O, W, H, cfg.divisor, cfg.sd_guard_px, cfg.radius)
+            self.sdp = O.SDParams(N, cfg.implementation, cfg.max_count, self.vao.sdGuard, 1, 1, 1, cfg.cull_mode, 0,
+                                  float(np.float32(1.5 / N)))
+            self.svp = O.SVAOParams(8, N, 2, 1, 1, cfg.guard_band)
+        if ss_max_radius is not None:  # a small sample reach: halo windows narrower than the map
+            self.vao.ssMaxRadius = ss_max_radius
+        self.z, self.n = O.gbuffer(self.osc, self.cam, W, H, cfg.cull_mode, threads=2)
+        self.np_ao = np.zeros((H, W), np.uint8)
+        self.np_st = np.zeros((H, W), np.uint8)
+        # rayMin / rayMax in one buffer, like rsd.frame.Renderer (one all-reduce per frame)
+        self.np_rminmax = np.zeros((2, self.sd_h, self.sd_w), np.uint32)
+        self.np_rmin, self.np_rmax = self.np_rminmax[0], self.np_rminmax[1]
+        self.np_sd = np.zeros(((N + 3) // 4, self.sd_h, self.sd_w, min(N, 4)), np.float32)
+        self.ao = torch.from_numpy(self.np_ao)
+        self.stencil = torch.from_numpy(self.np_st)
+        self.ray_minmax = torch.from_numpy(self.np_rminmax.view(np.int32))
+        self.ray_min, self.ray_max = self.ray_minmax[0], self.ray_minmax[1]
+        self.sd = torch.from_numpy(self.np_sd)
+
+    def clear_intervals(self):
+        self.O.svao_clear(self.np_rmin, self.np_rmax)
+
+    def pass1(self, band=(0, 1)):
+        self.O.svao_pass1_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_ao, self.np_st, self.np_rmin,
+                               self.np_rmax, band)
+
+    def sd_trace(self, band=(0, 1)):
+        self.O.sd_trace_into(self.osc, self.cam, self.sdp, self.z, self.np_rmin, self.np_rmax, self.np_sd, band,
+                             threads=2)
+
+    def pass2(self, band=(0, 1)):
+        self.O.svao_pass2_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_st, self.np_sd, self.np_ao, band,
+                               threads=2)
+
+    # contiguous bands (HaloFrame)
+    def pass1_rows(self, rows):
+        self.O.svao_pass1_rows_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_ao, self.np_st, self.np_rmin,
+                                    self.np_rmax, rows)
+
+    def sd_trace_rows(self, rows):
+        self.O.sd_trace_rows_into(self.osc, self.cam, self.sdp, self.z, self.np_rmin, self.np_rmax, self.np_sd, rows,
+                                  threads=2)
+
+    def pass2_rows(self, rows):
+        self.O.svao_pass2_rows_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_st, self.np_sd, self.np_ao,
+                                    rows, threads=2)
+
+
+def free_port():
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+# ---- the N > 1 band frame away from the benchmark shapes (test_band_odd.py checks on the oracle and on
+# HaloFrame._plan alone that the cases reach what they are meant to reach; test_gpu_band_odd.py runs
+# rsd_band_frame_front / _back on them)
+
+class BandOddCase(NamedTuple):
+    frame: str       # an ODD_FRAMES name, or BAND_TALL_FRAME's
+    world: int
+    sd_split: str    # "tiles" or "rows"
+    reach: float     # ssMaxRadius in pixels
+
+
+BAND_REACH_WHOLE = 512.0   # the default ssMaxRadius: every window covers the whole of these small maps
+BAND_REACH_SMALL = 24.0    # SVAO_SWEEP's clamping value: windows of a few dozen rows
+
+# A window that neither map edge clips needs more rows than any ODD_FRAMES shape has: at a reach of 24 px the sample
+# reach is 40 to 60 rows of the frame buffer either way (rsd.shard.halo_px), the tallest odd frame has 103.  This one
+# is tall and narrow instead: 37 x 203 visible (7 groups, the last of 11 rows), guard 3, divisor 2, sdGuard 5 / 2 = 2,
+# SD map 26 x 109
+BAND_TALL_FRAME = OddFrame("tall_div2", 37, 203, 3, 2, 5, 2.0)
+
+
+def band_frame_shape(name):
+    return BAND_TALL_FRAME if name == BAND_TALL_FRAME.name else odd_frame(name)
+
+
+def band_odd_worlds(f):
+    """2, 3, 5 and one more than the frame has 32-row groups (at least one rank without a row)."""
+    return sorted({2, 3, 5, -(-f.visible_h // 32) + 1})
+
+
+def _band_odd_cases():
+    # one (split, reach) per (frame, world), dealt in turn so that each reach meets each split on every frame with
+    # four worlds and over the table in any case
+    kinds = [("tiles", BAND_REACH_WHOLE), ("rows", BAND_REACH_SMALL), ("rows", BAND_REACH_WHOLE),
+             ("tiles", BAND_REACH_SMALL)]
+    cases, i = [], 0
+    for f in ODD_FRAMES:
+        for world in band_odd_worlds(f):
+            cases.append(BandOddCase(f.name, world, *kinds[i % 4]))
+            i += 1
+    # the tall frame at the small reach only (its whole-map windows add nothing to the odd frames')
+    cases += [BandOddCase(BAND_TALL_FRAME.name, 3, "tiles", BAND_REACH_SMALL),
+              BandOddCase(BAND_TALL_FRAME.name, 5, "rows", BAND_REACH_SMALL)]
+    return cases
+
+
+BAND_ODD_CASES = _band_odd_cases()
+
+
+def band_case_id(c):
+    return f"{c.frame}_w{c.world}_{c.sd_split}_r{c.reach:g}"
+
+
+class NoComm:
+    """The communicator of a HaloFrame that only plans (no frame is run)."""
+    nccl = False
+
+
+def band_plans(backend, world, sd_split):
+    """HaloFrame's partition of `backend`'s frame as every rank of `world` sees it (nothing is exchanged)."""
+    from rsd.shard import HaloFrame
+    return [HaloFrame(backend, r, world, comm=NoComm(), rebalance=False, sd_split=sd_split) for r in range(world)]
+
+
+def band_region_rows(plan, region):
+    """The SD rows of a send / receive region of a plan (None: no rows)."""
+    if not region:
+        return []
+    return plan._region_rows(region[0], region[1], plan.world if plan.sd_split == "tiles" else 1)
+
+
+def band_touched(backend, rows):
+    """The SD texels that pass 1 of the visible rows `rows` touches on cleared interval maps (rayMin no longer
+    asuint(FLT_MAX), or rayMax no longer 0), on the oracle."""
+    O = backend.O
+    rmin, rmax = np.zeros_like(backend.np_rmin), np.zeros_like(backend.np_rmax)
+    O.svao_clear(rmin, rmax)
+    ao, st = np.zeros_like(backend.np_ao), np.zeros_like(backend.np_st)
+    O.svao_pass1_rows_into(backend.cam, backend.vao, backend.svp, backend.z, backend.n, ao, st, rmin, rmax, rows)
+    return (rmin != 0x7F7FFFFF) | (rmax != 0)
+
+
+def band_odd_backend(O, c, scene=None):
+    """The oracle backend of a BAND_ODD_CASES entry over arcade_tiny."""
+    from rsd.scenes import make_scene
+    return OracleBackend(O, scene or make_scene("arcade_tiny"), odd_frame_config(band_frame_shape(c.frame)), c.reach,
+                         whole_config=True)
+
+
+# ---- the band frame over moving scenes (test_band_odd.py: the steps differ; test_gpu_band_odd.py: the frames)
+
+def moved_positions(scene, seed, part=(0.4, 0.3, -0.5)):
+    """Per-vertex jitter of a fixed seed plus the last eighth of the triangles translated by `part`."""
+    rng = np.random.default_rng(seed)
+    p = scene.positions + (0.02 * rng.standard_normal(scene.positions.shape)).astype(np.float32)
+    v = np.unique(scene.indices[-max(1, scene.indices.shape[0] // 8):])
+    p[v] += np.float32(part)
+    return np.ascontiguousarray(p, np.float32)
+
+
+BAND_MOVING_WORLD = 3
+# 1.9 is past the last keyframe (1.5): both animations cycle.  (From rest, t = 0.37 moves 86 SD texels of the oracle's
+# map at band_moving_config(), below the 100 that test_band_odd.py asks of neighbouring steps; these move 116 to 138.)
+TURNSTILE_TIMES = (0.6, 1.1, 1.9)
+
+
+def band_moving_config():
+    """SVAO_RAGGED_VISIBLE: 200 x 120 visible, guard 16, divisor 2, N = 4."""
+    return small_frame_config(visible=SVAO_RAGGED_VISIBLE, guard=16, divisor=2, N=4)
+
+
+def band_dynamic_steps(scene):
+    """The positions of the dynamic sequence: P0, P1 (update_positions), P2 (update_subset of the vertices in which
+    P1 and P2 differ), P0 again -- as (name, positions); the subset's ids are band_subset_ids(P1, P2)."""
+    p0 = np.ascontiguousarray(scene.positions, np.float32)
+    return [("P0", p0), ("P1", moved_positions(scene, 1)), ("P2", moved_positions(scene, 2)), ("P0 again", p0)]
+
+
+def band_subset_ids(a, b):
+    return np.flatnonzero((a != b).any(axis=1)).astype(np.uint32)
+
+
+def turnstile_steps():
+    """The built turnstile scene (with its rig) and its positions at rest and at TURNSTILE_TIMES, posed by
+    tests/skinning_checker.py -- as (scene, [(name, positions)])."""
+    from pathlib import Path
+
+    import skinning_checker
+    from rsd.pyscene import load_pyscene
+    scene = load_pyscene(Path(__file__).resolve().parent / "fixtures" / "turnstile.pyscene").build("turnstile")
+    assert scene.rig is not None
+    steps = [("rest", np.ascontiguousarray(scene.positions, np.float32))]
+    steps += [(f"t = {t:g}", skinning_checker.posed(scene.positions, scene.rig, scene.rig.matrices(t)))
+              for t in TURNSTILE_TIMES]
+    return scene, steps

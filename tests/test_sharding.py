@@ -4,72 +4,13 @@ The GPU backend of BandFrame is librsd (bench.py, tests/test_gpu_parity.py); her
 orchestration runs with the CPU oracle as backend in world_size 2 and 3 processes, and the
 gathered frame must be bit-identical to a single-process oracle frame."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
 
-from helpers import oracle_vao, small_frame_config
-
-
-class OracleBackend:
-    """BandFrame backend on the CPU oracle; numpy buffers shared with torch tensors."""
-
-    def __init__(self, O, scene, cfg, ss_max_radius=None):
-        self.O, self.cfg = O, cfg
-        self.osc = O.Scene(scene.positions, scene.indices, scene.flags)
-        W, H = cfg.fb_w, cfg.fb_h
-        aspect = float(np.float32(W) / np.float32(H))
-        self.cam = O.camera_look_at(scene.camera["pos"], scene.camera["target"], scene.camera["up"], aspect=aspect)
-        self.vao, self.sd_w, self.sd_h = oracle_vao(O, W, H, cfg.divisor, cfg.sd_guard_px, cfg.radius)
-        if ss_max_radius is not None:  # a small sample reach: halo windows narrower than the map
-            self.vao.ssMaxRadius = ss_max_radius
-        N = cfg.sd_samples
-        self.sdp = O.SDParams(N, cfg.implementation, cfg.max_count, self.vao.sdGuard, 1, 1, 1, cfg.cull_mode, 0,
-                              float(np.float32(1.5 / N)))
-        self.svp = O.SVAOParams(8, N, 2, 1, 1, cfg.guard_band)
-        self.z, self.n = O.gbuffer(self.osc, self.cam, W, H, cfg.cull_mode, threads=2)
-        self.np_ao = np.zeros((H, W), np.uint8)
-        self.np_st = np.zeros((H, W), np.uint8)
-        # rayMin / rayMax in one buffer, like rsd.frame.Renderer (one all-reduce per frame)
-        self.np_rminmax = np.zeros((2, self.sd_h, self.sd_w), np.uint32)
-        self.np_rmin, self.np_rmax = self.np_rminmax[0], self.np_rminmax[1]
-        self.np_sd = np.zeros(((N + 3) // 4, self.sd_h, self.sd_w, min(N, 4)), np.float32)
-        self.ao = torch.from_numpy(self.np_ao)
-        self.stencil = torch.from_numpy(self.np_st)
-        self.ray_minmax = torch.from_numpy(self.np_rminmax.view(np.int32))
-        self.ray_min, self.ray_max = self.ray_minmax[0], self.ray_minmax[1]
-        self.sd = torch.from_numpy(self.np_sd)
-
-    def clear_intervals(self):
-        self.O.svao_clear(self.np_rmin, self.np_rmax)
-
-    def pass1(self, band=(0, 1)):
-        self.O.svao_pass1_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_ao, self.np_st, self.np_rmin,
-                               self.np_rmax, band)
-
-    def sd_trace(self, band=(0, 1)):
-        self.O.sd_trace_into(self.osc, self.cam, self.sdp, self.z, self.np_rmin, self.np_rmax, self.np_sd, band,
-                             threads=2)
-
-    def pass2(self, band=(0, 1)):
-        self.O.svao_pass2_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_st, self.np_sd, self.np_ao, band,
-                               threads=2)
-
-    # contiguous bands (HaloFrame)
-    def pass1_rows(self, rows):
-        self.O.svao_pass1_rows_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_ao, self.np_st, self.np_rmin,
-                                    self.np_rmax, rows)
-
-    def sd_trace_rows(self, rows):
-        self.O.sd_trace_rows_into(self.osc, self.cam, self.sdp, self.z, self.np_rmin, self.np_rmax, self.np_sd, rows,
-                                  threads=2)
-
-    def pass2_rows(self, rows):
-        self.O.svao_pass2_rows_into(self.cam, self.vao, self.svp, self.z, self.n, self.np_st, self.np_sd, self.np_ao,
-                                    rows, threads=2)
+from helpers import OracleBackend, free_port as _free_port, oracle_vao, small_frame_config
 
 
 def _cfg():
@@ -143,14 +84,6 @@ def _lag_frames(O, cfg, rank, world, out_dir):
         if len(pending) > 1:
             finish(pending.pop(0))
     finish(pending.pop(0))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 @pytest.mark.parametrize("world", [2, 3])
