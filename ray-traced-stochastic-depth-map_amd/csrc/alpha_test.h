@@ -15,28 +15,10 @@
 
 namespace rsd {
 
-__device__ __forceinline__ float alpha_texel(const uint8_t* __restrict__ lvl, int w, int h, int x, int y) {
-    x %= w;
-    y %= h;
-    x += x < 0 ? w : 0;
-    y += y < 0 ? h : 0;
-    return (float)lvl[(size_t)y * w + x] / 255.0f;
-}
-
-// bilinear, wrap, 8 sub-texel bits (the linearZ sampler convention of rsd_device.h)
+// bilinear of one R8Unorm mip, wrap (tex_sample.h's rule, all four taps)
 __device__ __forceinline__ float alpha_bilinear(const uint8_t* __restrict__ lvl, int w, int h, float u, float v) {
-    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
-    const float fx0 = floorf(x), fy0 = floorf(y);
-    float qx = floorf((x - fx0) * 256.0f + 0.5f), qy = floorf((y - fy0) * 256.0f + 0.5f);
-    int ix = (int)fx0, iy = (int)fy0;
-    if (qx >= 256.0f) { ix += 1; qx = 0.0f; }
-    if (qy >= 256.0f) { iy += 1; qy = 0.0f; }
-    const float wx = qx * (1.0f / 256.0f), wy = qy * (1.0f / 256.0f);
-    const float t00 = alpha_texel(lvl, w, h, ix, iy), t10 = alpha_texel(lvl, w, h, ix + 1, iy);
-    const float t01 = alpha_texel(lvl, w, h, ix, iy + 1), t11 = alpha_texel(lvl, w, h, ix + 1, iy + 1);
-    const float r0 = t00 * (1.0f - wx) + t10 * wx;
-    const float r1 = t01 * (1.0f - wx) + t11 * wx;
-    return r0 * (1.0f - wy) + r1 * wy;
+    const TexSplit s = tex_split(w, h, u, v);
+    return unorm8_bilinear_at(lvl, s, tex_taps(s, w, h, true));
 }
 
 // SampleLevel(uv, level): trilinear between the two nearest mips, LOD clamped to the chain
@@ -44,10 +26,9 @@ __device__ __forceinline__ float alpha_sample(const AlphaData& A, uint32_t texIn
     const uint4 tx = A.textures[texIndex];
     const int mips = (int)tx.z;
     float lod = level != level ? 0.0f : fminf(fmaxf(level, 0.0f), (float)(mips - 1));
-    int l0 = (int)floorf(lod);
-    float qf = floorf((lod - (float)l0) * 256.0f + 0.5f);
-    if (qf >= 256.0f) { l0 += 1; qf = 0.0f; }
-    const float f = qf * (1.0f / 256.0f);
+    const TexAxis m = tex_split_axis(lod);  // the LOD fraction has the sampler's 8 bits
+    const int l0 = m.i;
+    const float qf = m.q, f = m.w;
     size_t off = tx.w;
     int w = (int)tx.x, h = (int)tx.y;
     for (int m = 0; m < l0; ++m) {

@@ -37,8 +37,7 @@
 namespace rsd {
 namespace {
 
-constexpr int kResolveW = 64, kResolveH = 4;  // post.hip's block shape
-constexpr int kMaxRadius = 20;                // AOGuidedBlur.cpp:180
+constexpr int kMaxRadius = 20;  // AOGuidedBlur.cpp:180
 
 struct GuidedArgs {
     const uint8_t* src;   // the pass's gSrcTex: the source (x pass) or the ping-pong image (y pass)
@@ -48,15 +47,9 @@ struct GuidedArgs {
     int qw, qh, g, R;
     int srcTexel;  // bytes per source texel: 1 (R8Unorm) or 2 (RG8Unorm)
     uint32_t localDeviation;
-    float uvMinX, uvMinY, uvMaxX, uvMaxY;
+    GuardUv uv;
     float spatial[2 * kMaxRadius + 1];  // kernel(R - it, SPATIAL_VARIANCE) (:123)
 };
-
-// Texel of a point sample with clamp addressing (the uv is finite and inside [0, 1] after the clamp)
-__device__ __forceinline__ int resolve_texel(float uv, int n) {
-    const int t = (int)floorf(uv * (float)n);
-    return t < 0 ? 0 : (t > n - 1 ? n - 1 : t);
-}
 
 // kernel(offset, variance) (:60-63) for the depth weight: DEPTH_VARIANCE 0.001
 __device__ __forceinline__ float depth_kernel(float offset) {
@@ -76,16 +69,16 @@ __device__ __forceinline__ uchar4 load_texel4(const uint8_t* __restrict__ t, siz
 }
 
 template <bool YPASS>
-__global__ void __launch_bounds__(kResolveW * kResolveH) ao_guided_blur_kernel(GuidedArgs a) {
-    const int x = a.g + (int)(blockIdx.x * kResolveW + threadIdx.x);
-    const int y = a.g + (int)(blockIdx.y * kResolveH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) ao_guided_blur_kernel(GuidedArgs a) {
+    const int x = a.g + (int)(blockIdx.x * kImageBlockW + threadIdx.x);
+    const int y = a.g + (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.qw - a.g || y >= a.qh - a.g) return;  // guard-band scissor on the layer (AOGuidedBlur.cpp:150)
     const size_t plane = (size_t)a.qw * a.qh, base = (size_t)blockIdx.z * plane;
     const float* __restrict__ z = a.z + base;
     const uint8_t* __restrict__ src = a.src + base * (YPASS ? 4 : a.srcTexel);
     const float tcx = ((float)x + 0.5f) / (float)a.qw, tcy = ((float)y + 0.5f) / (float)a.qh;
-    const float ccx = fminf(fmaxf(tcx, a.uvMinX), a.uvMaxX), ccy = fminf(fmaxf(tcy, a.uvMinY), a.uvMaxY);
-    const size_t centre = (size_t)resolve_texel(ccy, a.qh) * a.qw + resolve_texel(ccx, a.qw);
+    const float ccx = fminf(fmaxf(tcx, a.uv.minX), a.uv.maxX), ccy = fminf(fmaxf(tcy, a.uv.minY), a.uv.maxY);
+    const size_t centre = (size_t)tex_point(ccy, a.qh) * a.qw + tex_point(ccx, a.qw);
     const float localDepth = fmaxf(z[centre], __uint_as_float(1u));  // :110
     const uchar4 local = load_texel4<YPASS>(src, centre, a.srcTexel);  // :111
     const float localX = unorm8_to_float(local.x), localY = unorm8_to_float(local.y);
@@ -94,8 +87,8 @@ __global__ void __launch_bounds__(kResolveW * kResolveH) ao_guided_blur_kernel(G
     float u = tcx - stepX * (float)a.R, v = tcy - stepY * (float)a.R;  // :118
     float meanX = 0.0f, meanY = 0.0f, sqX = 0.0f, sqY = 0.0f, weightSum = 0.0f;
     for (int it = 0; it <= 2 * a.R; ++it) {
-        const float cu = fminf(fmaxf(u, a.uvMinX), a.uvMaxX), cv = fminf(fmaxf(v, a.uvMinY), a.uvMaxY);
-        const size_t tap = (size_t)resolve_texel(cv, a.qh) * a.qw + resolve_texel(cu, a.qw);
+        const float cu = fminf(fmaxf(u, a.uv.minX), a.uv.maxX), cv = fminf(fmaxf(v, a.uv.minY), a.uv.maxY);
+        const size_t tap = (size_t)tex_point(cv, a.qh) * a.qw + tex_point(cu, a.qw);
         const uchar4 t = load_texel4<YPASS>(src, tap, a.srcTexel);
         const float aoX = unorm8_to_float(t.x), aoY = unorm8_to_float(t.y);
         // :125-127 the y pass finds the squares in the last two channels
@@ -152,43 +145,19 @@ struct VarianceArgs {
     const float* z;
     uint8_t* dst;
     int qw, qh, g;
-    float uvMinX, uvMinY, uvMaxX, uvMaxY;
+    GuardUv uv;
     float spatial;  // kernel(1, 10) * kernel(0, 10) (:56), the same for the four neighbours
 };
 
-// The linear / clamp sampler (AOVarianceFix.cpp:57), librsd's bilinear rule: post.hip's unorm8_bilinear (8-bit
-// sub-texel weights, all four taps), restated over both images of the pair and, below, its float twin
-struct Footprint {
-    size_t t00, t10, t01, t11;
-    float wx, wy;
-};
-__device__ __forceinline__ Footprint footprint(int W, int H, float u, float v) {
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx0 = floorf(x), fy0 = floorf(y);
-    float qx = floorf((x - fx0) * 256.0f + 0.5f), qy = floorf((y - fy0) * 256.0f + 0.5f);
-    int ix = (int)fx0, iy = (int)fy0;
-    if (qx >= 256.0f) { ix += 1; qx = 0.0f; }
-    if (qy >= 256.0f) { iy += 1; qy = 0.0f; }
-    const int x0 = min(max(ix, 0), W - 1), x1 = min(max(ix + 1, 0), W - 1);
-    const int y0 = min(max(iy, 0), H - 1), y1 = min(max(iy + 1, 0), H - 1);
-    return Footprint{(size_t)y0 * W + x0, (size_t)y0 * W + x1, (size_t)y1 * W + x0, (size_t)y1 * W + x1,
-                     qx * (1.0f / 256.0f), qy * (1.0f / 256.0f)};
-}
-__device__ __forceinline__ float lerp4(const Footprint& f, float t00, float t10, float t01, float t11) {
-    const float r0 = t00 * (1.0f - f.wx) + t10 * f.wx, r1 = t01 * (1.0f - f.wx) + t11 * f.wx;
-    return r0 * (1.0f - f.wy) + r1 * f.wy;
-}
-__device__ __forceinline__ float unorm8_bilinear_at(const uint8_t* __restrict__ t, const Footprint& f) {
-    return lerp4(f, unorm8_to_float(t[f.t00]), unorm8_to_float(t[f.t10]), unorm8_to_float(t[f.t01]),
-                 unorm8_to_float(t[f.t11]));
-}
-__device__ __forceinline__ float float_bilinear_at(const float* __restrict__ t, const Footprint& f) {
-    return lerp4(f, t[f.t00], t[f.t10], t[f.t01], t[f.t11]);
+// The linear / clamp sampler (AOVarianceFix.cpp:57): tex_sample.h's rule, all four taps.  A tap's footprint is
+// split and addressed once for its three images: depth here, bright and dark through unorm8_bilinear_at
+__device__ __forceinline__ float float_bilinear_at(const float* __restrict__ t, const TexSplit& s, const TexTaps& p) {
+    return tex_lerp(s, t[p.t00], t[p.t10], t[p.t01], t[p.t11]);
 }
 
-__global__ void __launch_bounds__(kResolveW * kResolveH) ao_variance_fix_kernel(VarianceArgs a) {
-    const int x = a.g + (int)(blockIdx.x * kResolveW + threadIdx.x);
-    const int y = a.g + (int)(blockIdx.y * kResolveH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) ao_variance_fix_kernel(VarianceArgs a) {
+    const int x = a.g + (int)(blockIdx.x * kImageBlockW + threadIdx.x);
+    const int y = a.g + (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.qw - a.g || y >= a.qh - a.g) return;  // guard-band scissor on the layer (AOVarianceFix.cpp:144)
     const size_t base = (size_t)blockIdx.z * ((size_t)a.qw * a.qh);
     const float* __restrict__ z = a.z + base;
@@ -196,22 +165,24 @@ __global__ void __launch_bounds__(kResolveW * kResolveH) ao_variance_fix_kernel(
     const uint8_t* __restrict__ dark = a.dark + base;
     const float tcx = ((float)x + 0.5f) / (float)a.qw, tcy = ((float)y + 0.5f) / (float)a.qh;
     const float stepX = 1.0f / (float)a.qw, stepY = 1.0f / (float)a.qh;  // :45-47
-    const Footprint fc = footprint(a.qw, a.qh, fminf(fmaxf(tcx, a.uvMinX), a.uvMaxX),
-                                   fminf(fmaxf(tcy, a.uvMinY), a.uvMaxY));
-    const float localDepth = fmaxf(float_bilinear_at(z, fc), __uint_as_float(1u));  // :39
-    const float localX = unorm8_bilinear_at(bright, fc), localY = unorm8_bilinear_at(dark, fc);
+    const TexSplit sc = tex_split(a.qw, a.qh, fminf(fmaxf(tcx, a.uv.minX), a.uv.maxX),
+                                  fminf(fmaxf(tcy, a.uv.minY), a.uv.maxY));
+    const TexTaps pc = tex_taps(sc, a.qw, a.qh, false);
+    const float localDepth = fmaxf(float_bilinear_at(z, sc, pc), __uint_as_float(1u));  // :39
+    const float localX = unorm8_bilinear_at(bright, sc, pc), localY = unorm8_bilinear_at(dark, sc, pc);
     float meanX = localX, meanY = localY, weightSum = 1.0f;
     constexpr float ox[4] = {-1.0f, 0.0f, 1.0f, 0.0f}, oy[4] = {0.0f, -1.0f, 0.0f, 1.0f};  // :50
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const float u = tcx + ox[it] * stepX, v = tcy + oy[it] * stepY;  // :53
-        const Footprint f = footprint(a.qw, a.qh, fminf(fmaxf(u, a.uvMinX), a.uvMaxX),
-                                      fminf(fmaxf(v, a.uvMinY), a.uvMaxY));
-        const float relativeDepth = saturate(fabsf(float_bilinear_at(z, f) / localDepth - 1.0f));  // :58
-        const float w = a.spatial * 1.0f * depth_kernel(relativeDepth);                            // :62
+        const TexSplit s = tex_split(a.qw, a.qh, fminf(fmaxf(u, a.uv.minX), a.uv.maxX),
+                                     fminf(fmaxf(v, a.uv.minY), a.uv.maxY));
+        const TexTaps p = tex_taps(s, a.qw, a.qh, false);
+        const float relativeDepth = saturate(fabsf(float_bilinear_at(z, s, p) / localDepth - 1.0f));  // :58
+        const float w = a.spatial * 1.0f * depth_kernel(relativeDepth);                               // :62
         weightSum += w;
-        meanX += w * unorm8_bilinear_at(bright, f);
-        meanY += w * unorm8_bilinear_at(dark, f);
+        meanX += w * unorm8_bilinear_at(bright, s, p);
+        meanY += w * unorm8_bilinear_at(dark, s, p);
     }
     const float norm = fmaxf(weightSum, 1e-4f);  // :85
     meanX /= norm;
@@ -240,7 +211,7 @@ float host_kernel(float offset, float variance) { return (float)std::exp((double
 // The layer extent, the scissor on it and the GuardBand pass's uv bounds of the full-size frame
 struct LayerRect {
     int qw, qh, g;
-    float uvMinX, uvMinY, uvMaxX, uvMaxY;
+    GuardUv uv;
     bool empty;
 };
 LayerRect layer_rect(uint32_t width, uint32_t height, uint32_t layers, uint32_t guard_band) {
@@ -250,17 +221,10 @@ LayerRect layer_rect(uint32_t width, uint32_t height, uint32_t layers, uint32_t 
     // AOGuidedBlur.cpp:145-148
     r.g = (int)(layers > 1 ? guard_band / (uint32_t)(int)(std::sqrt((double)layers) + 0.5) : guard_band);
     r.empty = 2 * (int64_t)r.g >= r.qw || 2 * (int64_t)r.g >= r.qh;
-    // GuardBand.cpp:62-63
-    r.uvMinX = ((float)guard_band + 0.5f) / (float)width;
-    r.uvMinY = ((float)guard_band + 0.5f) / (float)height;
-    r.uvMaxX = ((float)width - ((float)guard_band + 0.5f)) / (float)width;
-    r.uvMaxY = ((float)height - ((float)guard_band + 0.5f)) / (float)height;
+    r.uv = guard_uv(width, height, guard_band);
     return r;
 }
-dim3 resolve_grid(const LayerRect& r, uint32_t layers) {
-    return dim3((uint32_t)(r.qw - 2 * r.g + kResolveW - 1) / kResolveW,
-                (uint32_t)(r.qh - 2 * r.g + kResolveH - 1) / kResolveH, layers);
-}
+dim3 resolve_grid(const LayerRect& r, uint32_t layers) { return image_grid(r.qw - 2 * r.g, r.qh - 2 * r.g, layers); }
 
 }  // namespace
 }  // namespace rsd
@@ -301,23 +265,19 @@ extern "C" rsd_status rsd_ao_guided_blur(const rsd_ao_guided_blur_params* params
     a.R = (int)params->kernel_radius;
     a.srcTexel = (int)params->src_texel_bytes;
     a.localDeviation = params->local_deviation ? 1u : 0u;
-    a.uvMinX = r.uvMinX;
-    a.uvMinY = r.uvMinY;
-    a.uvMaxX = r.uvMaxX;
-    a.uvMaxY = r.uvMaxY;
+    a.uv = r.uv;
     for (int it = 0; it <= 2 * a.R; ++it) a.spatial[it] = host_kernel((float)(a.R - it), 16.4f);  // SPATIAL_VARIANCE
-    const dim3 grid = resolve_grid(r, params->layers), block(kResolveW, kResolveH);
+    const dim3 grid = resolve_grid(r, params->layers);
     hipStream_t s = (hipStream_t)stream;
     a.src = d_src;  // blur in x (AOGuidedBlur.cpp:161-165)
     a.dst = d_pingpong;
-    hipLaunchKernelGGL(ao_guided_blur_kernel<false>, grid, block, 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "ao_guided_blur_kernel (x) launch");
+    hipLaunchKernelGGL(ao_guided_blur_kernel<false>, grid, image_block(), 0, s, a);
+    const rsd_status st = launch_status("ao_guided_blur_kernel (x) launch");
+    if (st != RSD_OK) return st;
     a.src = d_pingpong;  // blur in y (:167-171)
     a.dst = d_dst;
-    hipLaunchKernelGGL(ao_guided_blur_kernel<true>, grid, block, 0, s, a);
-    e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "ao_guided_blur_kernel (y) launch");
+    hipLaunchKernelGGL(ao_guided_blur_kernel<true>, grid, image_block(), 0, s, a);
+    return launch_status("ao_guided_blur_kernel (y) launch");
 }
 
 extern "C" rsd_status rsd_ao_first_channel(const uint8_t* d_src, uint32_t src_texel_bytes, uint64_t texels,
@@ -332,8 +292,7 @@ extern "C" rsd_status rsd_ao_first_channel(const uint8_t* d_src, uint32_t src_te
     }
     hipLaunchKernelGGL(ao_first_channel_kernel, dim3((uint32_t)((texels + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, d_src, src_texel_bytes, texels, d_dst);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "ao_first_channel_kernel launch");
+    return launch_status("ao_first_channel_kernel launch");
 }
 
 extern "C" rsd_status rsd_ao_variance_fix(const rsd_ao_variance_fix_params* params, const uint8_t* d_bright,
@@ -361,13 +320,8 @@ extern "C" rsd_status rsd_ao_variance_fix(const rsd_ao_variance_fix_params* para
     a.qw = r.qw;
     a.qh = r.qh;
     a.g = r.g;
-    a.uvMinX = r.uvMinX;
-    a.uvMinY = r.uvMinY;
-    a.uvMaxX = r.uvMaxX;
-    a.uvMaxY = r.uvMaxY;
+    a.uv = r.uv;
     a.spatial = host_kernel(1.0f, 10.0f) * host_kernel(0.0f, 10.0f);
-    hipLaunchKernelGGL(ao_variance_fix_kernel, resolve_grid(r, params->layers), dim3(kResolveW, kResolveH), 0,
-                       (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "ao_variance_fix_kernel launch");
+    hipLaunchKernelGGL(ao_variance_fix_kernel, resolve_grid(r, params->layers), image_block(), 0, (hipStream_t)stream, a);
+    return launch_status("ao_variance_fix_kernel launch");
 }

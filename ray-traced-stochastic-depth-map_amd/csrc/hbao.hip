@@ -25,7 +25,6 @@
 namespace rsd {
 namespace {
 
-constexpr int kHbaoW = 64, kHbaoH = 4;  // post.hip's block shape
 constexpr int kDirections = 8, kSteps = 4;  // HBAO.ps.slang:4-5
 
 struct HbaoArgs {
@@ -42,14 +41,6 @@ struct HbaoArgs {
     float dir[16][kDirections][2];                     // Rotate2D(Rand.xy, Alpha i) (:48-57, :171-174)
 };
 
-// Texel of a point sample with clamp addressing: floor(uv n) clamped while still a float, so no out-of-range
-// value is converted to an integer; a NaN coordinate addresses texel 0
-__device__ __forceinline__ int clamp_texel(float uv, int n) {
-    const float f = floorf(uv * (float)n);
-    if (!(f >= 0.0f)) return 0;
-    return f > (float)(n - 1) ? n - 1 : (int)f;
-}
-
 struct Shade {
     float px, py, pz, nx, ny, nz;  // ViewPosition, ViewNormal
     float negInvRsq, bias;
@@ -65,9 +56,9 @@ __device__ __forceinline__ float ao_terms(const Shade& s, float sx, float sy, fl
 }
 
 template <bool DUAL>
-__global__ void __launch_bounds__(kHbaoW * kHbaoH) hbao_kernel(HbaoArgs a) {
-    const int x = a.g + (int)(blockIdx.x * kHbaoW + threadIdx.x);
-    const int y = a.g + (int)(blockIdx.y * kHbaoH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) hbao_kernel(HbaoArgs a) {
+    const int x = a.g + (int)(blockIdx.x * kImageBlockW + threadIdx.x);
+    const int y = a.g + (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.qw - a.g || y >= a.qh - a.g) return;  // guard-band scissor on the quarter target (HBAO.cpp:181)
     const int layer = (int)blockIdx.z;
     const size_t plane = (size_t)a.qw * a.qh;
@@ -77,7 +68,7 @@ __global__ void __launch_bounds__(kHbaoW * kHbaoH) hbao_kernel(HbaoArgs a) {
     // :137-138 svPos = floor(svPos) * 4 + quarterOffset + 0.5, texC = svPos * invResolution
     const float tcx = ((float)x * 4.0f + (float)(layer & 3) + 0.5f) * a.invResX;
     const float tcy = ((float)y * 4.0f + (float)(layer >> 2) + 0.5f) * a.invResY;
-    const float depth = z1[(size_t)clamp_texel(tcy, a.qh) * a.qw + clamp_texel(tcx, a.qw)];
+    const float depth = z1[(size_t)tex_point(tcy, a.qh) * a.qw + tex_point(tcx, a.qw)];
     const uchar2 one = make_uchar2(255, 255);
     if (depth >= a.farZ) {  // :140
         *out = one;
@@ -88,7 +79,7 @@ __global__ void __launch_bounds__(kHbaoW * kHbaoH) hbao_kernel(HbaoArgs a) {
     s.px = ndcx * depth * a.isx;
     s.py = ndcy * depth * a.isy;
     s.pz = -depth;
-    const float4 nw = a.normal[(size_t)clamp_texel(tcy, a.H) * a.W + clamp_texel(tcx, a.W)];
+    const float4 nw = a.normal[(size_t)tex_point(tcy, a.H) * a.W + tex_point(tcx, a.W)];
     s.nx = a.view[0] * nw.x + a.view[1] * nw.y + a.view[2] * nw.z;  // mul(float3x3(viewMat), n) (:147)
     s.ny = a.view[3] * nw.x + a.view[4] * nw.y + a.view[5] * nw.z;
     s.nz = a.view[6] * nw.x + a.view[7] * nw.y + a.view[8] * nw.z;
@@ -116,7 +107,7 @@ __global__ void __launch_bounds__(kHbaoW * kHbaoH) hbao_kernel(HbaoArgs a) {
 #pragma unroll
         for (int k = 0; k < kSteps; ++k) {
             const float u = tcx + rintf(rayPixels * dx) * a.invQX, v = tcy + rintf(rayPixels * dy) * a.invQY;  // :183
-            const size_t tap = (size_t)clamp_texel(v, a.qh) * a.qw + clamp_texel(u, a.qw);
+            const size_t tap = (size_t)tex_point(v, a.qh) * a.qw + tex_point(u, a.qw);
             const float sndcx = u * 2.0f - 1.0f, sndcy = (1.0f - v) * 2.0f - 1.0f;
             const float d1 = z1[tap];
             float dist;
@@ -252,11 +243,10 @@ extern "C" rsd_status rsd_hbao(const float* d_depth_layers, const float* d_depth
             a.dir[s][i][1] = params->rand[s][0] * st + params->rand[s][1] * ct;
         }
     }
-    const dim3 grid((uint32_t)(a.qw - 2 * a.g + kHbaoW - 1) / kHbaoW, (uint32_t)(a.qh - 2 * a.g + kHbaoH - 1) / kHbaoH, 16);
+    const dim3 grid = image_grid(a.qw - 2 * a.g, a.qh - 2 * a.g, 16);
     if (params->depth_mode == 1u)
-        hipLaunchKernelGGL(hbao_kernel<true>, grid, dim3(kHbaoW, kHbaoH), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(hbao_kernel<true>, grid, image_block(), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(hbao_kernel<false>, grid, dim3(kHbaoW, kHbaoH), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "hbao_kernel launch");
+        hipLaunchKernelGGL(hbao_kernel<false>, grid, image_block(), 0, (hipStream_t)stream, a);
+    return launch_status("hbao_kernel launch");
 }

@@ -27,8 +27,6 @@ const IeProgram& image_program(const rsd_image_program* p);
 
 namespace {
 
-constexpr int kPostW = 64, kPostH = 4;
-
 // ---------------------------------------------------------------------- CrossBilateralBlur
 struct BlurArgs {
     const uint8_t* src;
@@ -37,30 +35,25 @@ struct BlurArgs {
     int W, H, g;
     int srcTexel;  // bytes per source texel; the blur reads byte 0 (CrossBilateralBlur.ps.slang:72 `.x`)
     float dirX, dirY;
-    float uvMinX, uvMinY, uvMaxX, uvMaxY;
+    GuardUv uv;
     int zW, zH;
     uint32_t betterSlope;
 };
 
-__device__ __forceinline__ int point_texel(float uv, int n) {
-    int t = (int)floorf(uv * (float)n);
-    return t < 0 ? 0 : (t > n - 1 ? n - 1 : t);
-}
-
 template <int R>
-__global__ void __launch_bounds__(kPostW * kPostH) blur_kernel(BlurArgs a) {
-    const int x = a.g + (int)(blockIdx.x * kPostW + threadIdx.x);
-    const int y = a.g + (int)(blockIdx.y * kPostH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) blur_kernel(BlurArgs a) {
+    const int x = a.g + (int)(blockIdx.x * kImageBlockW + threadIdx.x);
+    const int y = a.g + (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.W - a.g || y >= a.H - a.g) return;  // guard-band scissor
     const float tcx = ((float)x + 0.5f) / (float)a.W, tcy = ((float)y + 0.5f) / (float)a.H;
     const float dux = (1.0f / (float)a.W) * a.dirX, duy = (1.0f / (float)a.H) * a.dirY;
     float dc[2 * R + 1], ac[2 * R + 1];
 #pragma unroll
     for (int d = -R; d <= R; ++d) {
-        const float u = fminf(fmaxf(tcx + (float)d * dux, a.uvMinX), a.uvMaxX);
-        const float v = fminf(fmaxf(tcy + (float)d * duy, a.uvMinY), a.uvMaxY);
-        dc[R + d] = a.z[(size_t)point_texel(v, a.zH) * a.zW + point_texel(u, a.zW)];
-        ac[R + d] = unorm8_to_float(a.src[((size_t)point_texel(v, a.H) * a.W + point_texel(u, a.W)) * a.srcTexel]);
+        const float u = fminf(fmaxf(tcx + (float)d * dux, a.uv.minX), a.uv.maxX);
+        const float v = fminf(fmaxf(tcy + (float)d * duy, a.uv.minY), a.uv.maxY);
+        dc[R + d] = a.z[(size_t)tex_point(v, a.zH) * a.zW + tex_point(u, a.zW)];
+        ac[R + d] = unorm8_to_float(a.src[((size_t)tex_point(v, a.H) * a.W + tex_point(u, a.W)) * a.srcTexel]);
     }
     const float sigma = ((float)R + 1.0f) * 0.5f;
     const float falloff = 1.0f / (2.0f * sigma * sigma);
@@ -88,10 +81,9 @@ __global__ void __launch_bounds__(kPostW * kPostH) blur_kernel(BlurArgs a) {
 }
 
 template <int R>
-hipError_t launch_blur(const BlurArgs& a, hipStream_t s) {
-    const dim3 grid((a.W - 2 * a.g + kPostW - 1) / kPostW, (a.H - 2 * a.g + kPostH - 1) / kPostH);
-    hipLaunchKernelGGL(blur_kernel<R>, grid, dim3(kPostW, kPostH), 0, s, a);
-    return hipGetLastError();
+rsd_status launch_blur(const BlurArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(blur_kernel<R>, image_grid(a.W - 2 * a.g, a.H - 2 * a.g), image_block(), 0, s, a);
+    return launch_status("blur_kernel launch");
 }
 
 // ---------------------------------------------------------------------- TAA
@@ -123,32 +115,16 @@ __device__ __forceinline__ float4 taa_load(const float4* __restrict__ t, int W, 
     return t[(size_t)y * W + x];
 }
 
-__device__ __forceinline__ int wrap_addr(int i, int n) {
-    i %= n;
-    return i < 0 ? i + n : i;
-}
-
-// bilinear RGB of an RGBA32F texture, wrap addressing, 8-bit sub-texel weights (all 4 taps)
+// bilinear RGB of an RGBA32F texture, wrap addressing (all 4 taps)
 __device__ __forceinline__ f3 taa_bilinear(const float4* __restrict__ t, int W, int H, float u, float v) {
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx0 = floorf(x), fy0 = floorf(y);
-    float qx = floorf((x - fx0) * 256.0f + 0.5f), qy = floorf((y - fy0) * 256.0f + 0.5f);
-    int ix = (int)fx0, iy = (int)fy0;
-    if (qx >= 256.0f) { ix += 1; qx = 0.0f; }
-    if (qy >= 256.0f) { iy += 1; qy = 0.0f; }
-    const float wx = qx * (1.0f / 256.0f), wy = qy * (1.0f / 256.0f);
-    const int x0 = wrap_addr(ix, W), x1 = wrap_addr(ix + 1, W), y0 = wrap_addr(iy, H), y1 = wrap_addr(iy + 1, H);
-    const float4 a = t[(size_t)y0 * W + x0], b = t[(size_t)y0 * W + x1];
-    const float4 c = t[(size_t)y1 * W + x0], d = t[(size_t)y1 * W + x1];
-    auto lerp2 = [&](float p, float q, float r, float s) {
-        const float r0 = p * (1.0f - wx) + q * wx, r1 = r * (1.0f - wx) + s * wx;
-        return r0 * (1.0f - wy) + r1 * wy;
-    };
-    return mk(lerp2(a.x, b.x, c.x, d.x), lerp2(a.y, b.y, c.y, d.y), lerp2(a.z, b.z, c.z, d.z));
+    const TexSplit s = tex_split(W, H, u, v);
+    const TexTaps p = tex_taps(s, W, H, true);
+    const float4 a = t[p.t00], b = t[p.t10], c = t[p.t01], d = t[p.t11];
+    return mk(tex_lerp(s, a.x, b.x, c.x, d.x), tex_lerp(s, a.y, b.y, c.y, d.y), tex_lerp(s, a.z, b.z, c.z, d.z));
 }
 
-__global__ void __launch_bounds__(kPostW * kPostH) taa_kernel(TaaArgs a) {
-    const int x = (int)(blockIdx.x * kPostW + threadIdx.x), y = (int)(blockIdx.y * kPostH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) taa_kernel(TaaArgs a) {
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.W || y >= a.H) return;
     constexpr int ox[8] = {-1, -1, 1, 1, 1, 0, 0, -1}, oy[8] = {-1, 1, -1, 1, 0, -1, 1, 0};
     const float tu = ((float)x + 0.5f) / (float)a.W, tv = ((float)y + 0.5f) / (float)a.H;  // texC
@@ -234,10 +210,10 @@ template <>
 struct TexelT<16> { uint4 v; };
 
 template <int ELEM>
-__global__ void __launch_bounds__(kPostW * kPostH) deinterleave_kernel(const TexelT<ELEM>* __restrict__ src, int W,
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) deinterleave_kernel(const TexelT<ELEM>* __restrict__ src, int W,
                                                                         int H, TexelT<ELEM>* __restrict__ dst, int w4,
                                                                         int h4) {
-    const int x = (int)(blockIdx.x * kPostW + threadIdx.x), y = (int)(blockIdx.y * kPostH + threadIdx.y);
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= w4 || y >= h4) return;
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -249,10 +225,10 @@ __global__ void __launch_bounds__(kPostW * kPostH) deinterleave_kernel(const Tex
 }
 
 template <int ELEM>
-__global__ void __launch_bounds__(kPostW * kPostH) interleave_kernel(const TexelT<ELEM>* __restrict__ src, int w4,
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) interleave_kernel(const TexelT<ELEM>* __restrict__ src, int w4,
                                                                       int h4, TexelT<ELEM>* __restrict__ dst, int W,
                                                                       int H) {
-    const int x = (int)(blockIdx.x * kPostW + threadIdx.x), y = (int)(blockIdx.y * kPostH + threadIdx.y);
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= W || y >= H) return;
     const int xq = x >> 2, yq = y >> 2, s = (y & 3) * 4 + (x & 3);
     TexelT<ELEM> t{};
@@ -277,11 +253,11 @@ __global__ void __launch_bounds__(256) ray_length_kernel(const uint32_t* __restr
 // in y, one of its two neighbours lies in the plane of its view-space normal to within 0.1 (|dot|
 // of the unit offset with the normal).  Loads outside the image read 0; HLSL min returns the
 // non-NaN operand (a zero offset normalizes to NaN).
-__global__ void __launch_bounds__(kPostW * kPostH) flicker_mask_kernel(const float* __restrict__ z,
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) flicker_mask_kernel(const float* __restrict__ z,
                                                                         const float4* __restrict__ nw, int W, int H,
                                                                         rsd_camera cam, float isx, float isy,
                                                                         uint8_t* __restrict__ mask) {
-    const int x = (int)(blockIdx.x * kPostW + threadIdx.x), y = (int)(blockIdx.y * kPostH + threadIdx.y);
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= W || y >= H) return;
     auto ld = [&](int i, int j) { return (i < 0 || j < 0 || i >= W || j >= H) ? 0.0f : z[(size_t)j * W + i]; };
     auto view = [&](int i, int j, float d) {  // UVToViewSpace(PixelToUV(px), d)
@@ -306,24 +282,17 @@ __global__ void __launch_bounds__(kPostW * kPostH) flicker_mask_kernel(const flo
 // ---------------------------------------------------------------------- BinaryDilation
 // BinaryDilation.ps.slang:13-43: OP (min / max) over five Gather footprints (2x2 texels each):
 // the centre and four at (+-0.5, +-1.5) px offsets (a radius-2 ring).  Gather's footprint is the
-// bilinear footprint of the sample position (librsd's 8-bit sub-texel quantization), wrap
-// addressing (the unbound sampler S: Falcor's default).
+// bilinear footprint of the sample position (tex_sample.h, the carry included; the weights are not
+// used), wrap addressing (the unbound sampler S: Falcor's default).
 __device__ __forceinline__ uint32_t gather_op(const uint8_t* __restrict__ t, int W, int H, float u, float v, bool mx) {
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx0 = floorf(x), fy0 = floorf(y);
-    const float qx = floorf((x - fx0) * 256.0f + 0.5f), qy = floorf((y - fy0) * 256.0f + 0.5f);
-    int ix = (int)fx0, iy = (int)fy0;
-    if (qx >= 256.0f) ix += 1;
-    if (qy >= 256.0f) iy += 1;
-    const int x0 = wrap_addr(ix, W), x1 = wrap_addr(ix + 1, W), y0 = wrap_addr(iy, H), y1 = wrap_addr(iy + 1, H);
-    const uint32_t a = t[(size_t)y1 * W + x0], b = t[(size_t)y1 * W + x1], c = t[(size_t)y0 * W + x1],
-                   d = t[(size_t)y0 * W + x0];  // Gather order w, z, ... (irrelevant to min / max)
+    const TexTaps p = tex_taps(tex_split(W, H, u, v), W, H, true);
+    const uint32_t a = t[p.t01], b = t[p.t11], c = t[p.t10], d = t[p.t00];  // Gather order w, z, ... (irrelevant to min / max)
     return mx ? max(max(a, b), max(c, d)) : min(min(a, b), min(c, d));
 }
 
-__global__ void __launch_bounds__(kPostW * kPostH) binary_dilation_kernel(const uint8_t* __restrict__ in, int W, int H,
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) binary_dilation_kernel(const uint8_t* __restrict__ in, int W, int H,
                                                                            uint32_t opMax, uint8_t* __restrict__ out) {
-    const int x = (int)(blockIdx.x * kPostW + threadIdx.x), y = (int)(blockIdx.y * kPostH + threadIdx.y);
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= W || y >= H) return;
     const bool mx = opMax != 0u;
     const float u = ((float)x + 0.5f) / (float)W, v = ((float)y + 0.5f) / (float)H;
@@ -355,30 +324,13 @@ struct TaoArgs {
     uint8_t* nOut;
     int W, H, g;
     float m[16];  // prevViewToCurView, row-major
-    float uvMinX, uvMinY, uvMaxX, uvMaxY;
+    GuardUv uv;
     float isx, isy;  // 0.5 * frameWidth / focalLength, 0.5 * frameHeight / focalLength
 };
 
-// bilinear of an R8Unorm texture (clamp), librsd's sampler definition (tex_bilinear on unorm8/255)
-__device__ __forceinline__ float unorm8_bilinear(const uint8_t* __restrict__ t, int W, int H, float u, float v) {
-    float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx0 = floorf(x), fy0 = floorf(y);
-    float qx = floorf((x - fx0) * 256.0f + 0.5f), qy = floorf((y - fy0) * 256.0f + 0.5f);
-    int ix = (int)fx0, iy = (int)fy0;
-    if (qx >= 256.0f) { ix += 1; qx = 0.0f; }
-    if (qy >= 256.0f) { iy += 1; qy = 0.0f; }
-    const float wx = qx * (1.0f / 256.0f), wy = qy * (1.0f / 256.0f);
-    const int x0 = min(max(ix, 0), W - 1), x1 = min(max(ix + 1, 0), W - 1);
-    const int y0 = min(max(iy, 0), H - 1), y1 = min(max(iy + 1, 0), H - 1);
-    const float t00 = unorm8_to_float(t[(size_t)y0 * W + x0]), t10 = unorm8_to_float(t[(size_t)y0 * W + x1]);
-    const float t01 = unorm8_to_float(t[(size_t)y1 * W + x0]), t11 = unorm8_to_float(t[(size_t)y1 * W + x1]);
-    const float r0 = t00 * (1.0f - wx) + t10 * wx, r1 = t01 * (1.0f - wx) + t11 * wx;
-    return r0 * (1.0f - wy) + r1 * wy;
-}
-
-__global__ void __launch_bounds__(kPostW * kPostH) temporal_ao_kernel(TaoArgs a) {
-    const int x = a.g + (int)(blockIdx.x * kPostW + threadIdx.x);
-    const int y = a.g + (int)(blockIdx.y * kPostH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) temporal_ao_kernel(TaoArgs a) {
+    const int x = a.g + (int)(blockIdx.x * kImageBlockW + threadIdx.x);
+    const int y = a.g + (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.W - a.g || y >= a.H - a.g) return;  // guard-band scissor
     const size_t o = (size_t)y * a.W + x;
     const float tu = ((float)x + 0.5f) / (float)a.W, tv = ((float)y + 0.5f) / (float)a.H;  // texC
@@ -387,9 +339,8 @@ __global__ void __launch_bounds__(kPostW * kPostH) temporal_ao_kernel(TaoArgs a)
     uint32_t n = 1u;
     const float2 mv = a.mvec[o];
     const float pu = tu + mv.x, pv = tv + mv.y;
-    if (pu >= a.uvMinX && pu <= a.uvMaxX && pv >= a.uvMinY && pv <= a.uvMaxY) {  // isInValidArea
-        const int qx = (int)floorf(pu * (float)a.W), qy = (int)floorf(pv * (float)a.H);  // UVToPixel
-        const size_t po = (size_t)min(max(qy, 0), a.H - 1) * a.W + min(max(qx, 0), a.W - 1);
+    if (pu >= a.uv.minX && pu <= a.uv.maxX && pv >= a.uv.minY && pv <= a.uv.maxY) {  // isInValidArea
+        const size_t po = (size_t)tex_point(pv, a.H) * a.W + tex_point(pu, a.W);  // UVToPixel
         const float prevRaw = a.prevZ[po];
         // UVToViewSpace(texC + mvec, prevRawDepth), then prevViewToCurView
         const float ndcx = pu * 2.0f - 1.0f, ndcy = (1.0f - pv) * 2.0f - 1.0f;
@@ -398,7 +349,8 @@ __global__ void __launch_bounds__(kPostW * kPostH) temporal_ao_kernel(TaoArgs a)
         const float prevDepth = -pz;
         const bool stable = a.stable && a.stable[o] != 0u;
         if (fabsf(1.0f - prevDepth / depth) < 0.1f && !stable) {  // RelativeDepth(depth, prevDepth)
-            const float prevAo = unorm8_bilinear(a.prevAo, a.W, a.H, pu, pv);
+            const TexSplit s = tex_split(a.W, a.H, pu, pv);  // gAOSampler: linear, clamp
+            const float prevAo = unorm8_bilinear_at(a.prevAo, s, tex_taps(s, a.W, a.H, false));
             const uint32_t prevN = a.prevN[po];
             ao = ((float)prevN * prevAo + ao) / (float)(prevN + 1u);
             n = min(prevN + 1u, 30u);
@@ -424,8 +376,8 @@ struct MvecArgs {
     float pU[3], pV[3], pW[3];  // prev U / |U|^2, V / |V|^2, W / |W|^2
 };
 
-__global__ void __launch_bounds__(kPostW * kPostH) motion_vector_kernel(MvecArgs a) {
-    const int x = (int)(blockIdx.x * kPostW + threadIdx.x), y = (int)(blockIdx.y * kPostH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) motion_vector_kernel(MvecArgs a) {
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.W || y >= a.H) return;
     const rsd_camera& c = a.cam;
     const float u = ((float)x + 0.5f) / (float)a.W, v = ((float)y + 0.5f) / (float)a.H;
@@ -532,8 +484,8 @@ __device__ __forceinline__ float f2(int f, float a, float b) {
 }
 #define RSD_MAP4(e) make_float4(e(x), e(y), e(z), e(w))
 
-__global__ void __launch_bounds__(kPostW * kPostH) image_equation_kernel(EqArgs a) {
-    const int x = (int)(blockIdx.x * kPostW + threadIdx.x), y = (int)(blockIdx.y * kPostH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) image_equation_kernel(EqArgs a) {
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.W || y >= a.H) return;
     float4 st[kIeMaxStack];
     int sp = 0;
@@ -651,11 +603,7 @@ extern "C" rsd_status rsd_cross_bilateral_blur_src(const uint8_t* d_src, uint32_
     a.H = (int)height;
     a.g = (int)guard_band;
     a.betterSlope = better_slope ? 1u : 0u;
-    // GuardBand.cpp:62-63
-    a.uvMinX = ((float)guard_band + 0.5f) / (float)width;
-    a.uvMinY = ((float)guard_band + 0.5f) / (float)height;
-    a.uvMaxX = ((float)width - ((float)guard_band + 0.5f)) / (float)width;
-    a.uvMaxY = ((float)height - ((float)guard_band + 0.5f)) / (float)height;
+    a.uv = guard_uv(width, height, guard_band);
     hipStream_t s = (hipStream_t)stream;
     for (int pass = 0; pass < 2; ++pass) {  // blur in x into the ping-pong image, then in y
         a.src = pass == 0 ? d_src : d_pingpong;
@@ -663,14 +611,14 @@ extern "C" rsd_status rsd_cross_bilateral_blur_src(const uint8_t* d_src, uint32_
         a.dst = pass == 0 ? d_pingpong : d_dst;
         a.dirX = pass == 0 ? 1.0f : 0.0f;
         a.dirY = pass == 0 ? 0.0f : 1.0f;
-        hipError_t e = hipSuccess;
+        rsd_status st = RSD_OK;
         switch (kernel_radius) {
-#define RSD_R(r) case r: e = launch_blur<r>(a, s); break;
+#define RSD_R(r) case r: st = launch_blur<r>(a, s); break;
             RSD_R(1) RSD_R(2) RSD_R(3) RSD_R(4) RSD_R(5) RSD_R(6) RSD_R(7) RSD_R(8) RSD_R(9) RSD_R(10)
             RSD_R(11) RSD_R(12) RSD_R(13) RSD_R(14) RSD_R(15) RSD_R(16) RSD_R(17) RSD_R(18) RSD_R(19) RSD_R(20)
 #undef RSD_R
         }
-        if (e != hipSuccess) return hip_fail(e, "blur_kernel launch");
+        if (st != RSD_OK) return st;
     }
     return RSD_OK;
 }
@@ -688,17 +636,16 @@ template <template <int> class KERNEL>
 rsd_status launch_by_elem(uint32_t elem, dim3 grid, hipStream_t s, const void* src, int a0, int a1, void* dst, int b0,
                           int b1, const char* what) {
     switch (elem) {
-        case 1: hipLaunchKernelGGL(KERNEL<1>::fn, grid, dim3(kPostW, kPostH), 0, s, (const TexelT<1>*)src, a0, a1, (TexelT<1>*)dst, b0, b1); break;
-        case 2: hipLaunchKernelGGL(KERNEL<2>::fn, grid, dim3(kPostW, kPostH), 0, s, (const TexelT<2>*)src, a0, a1, (TexelT<2>*)dst, b0, b1); break;
-        case 4: hipLaunchKernelGGL(KERNEL<4>::fn, grid, dim3(kPostW, kPostH), 0, s, (const TexelT<4>*)src, a0, a1, (TexelT<4>*)dst, b0, b1); break;
-        case 8: hipLaunchKernelGGL(KERNEL<8>::fn, grid, dim3(kPostW, kPostH), 0, s, (const TexelT<8>*)src, a0, a1, (TexelT<8>*)dst, b0, b1); break;
-        case 16: hipLaunchKernelGGL(KERNEL<16>::fn, grid, dim3(kPostW, kPostH), 0, s, (const TexelT<16>*)src, a0, a1, (TexelT<16>*)dst, b0, b1); break;
+        case 1: hipLaunchKernelGGL(KERNEL<1>::fn, grid, image_block(), 0, s, (const TexelT<1>*)src, a0, a1, (TexelT<1>*)dst, b0, b1); break;
+        case 2: hipLaunchKernelGGL(KERNEL<2>::fn, grid, image_block(), 0, s, (const TexelT<2>*)src, a0, a1, (TexelT<2>*)dst, b0, b1); break;
+        case 4: hipLaunchKernelGGL(KERNEL<4>::fn, grid, image_block(), 0, s, (const TexelT<4>*)src, a0, a1, (TexelT<4>*)dst, b0, b1); break;
+        case 8: hipLaunchKernelGGL(KERNEL<8>::fn, grid, image_block(), 0, s, (const TexelT<8>*)src, a0, a1, (TexelT<8>*)dst, b0, b1); break;
+        case 16: hipLaunchKernelGGL(KERNEL<16>::fn, grid, image_block(), 0, s, (const TexelT<16>*)src, a0, a1, (TexelT<16>*)dst, b0, b1); break;
         default:
             set_error(std::string(what) + ": texel size must be 1, 2, 4, 8 or 16 bytes");
             return RSD_ERR_UNSUPPORTED;
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, what);
+    return launch_status(what);
 }
 template <int E>
 struct DeinterleaveK { static constexpr auto fn = deinterleave_kernel<E>; };
@@ -713,7 +660,7 @@ extern "C" rsd_status rsd_deinterleave(const void* d_src, uint32_t width, uint32
         return RSD_ERR_INVALID_ARG;
     }
     const uint32_t w4 = (width + 3) / 4, h4 = (height + 3) / 4;
-    const dim3 grid((w4 + kPostW - 1) / kPostW, (h4 + kPostH - 1) / kPostH);
+    const dim3 grid = image_grid(w4, h4);
     return launch_by_elem<DeinterleaveK>(texel_bytes, grid, (hipStream_t)stream, d_src, (int)width, (int)height, d_dst,
                                          (int)w4, (int)h4, "rsd_deinterleave");
 }
@@ -725,7 +672,7 @@ extern "C" rsd_status rsd_interleave(const void* d_src, uint32_t width, uint32_t
         return RSD_ERR_INVALID_ARG;
     }
     const uint32_t w4 = (width + 3) / 4, h4 = (height + 3) / 4;
-    const dim3 grid((width + kPostW - 1) / kPostW, (height + kPostH - 1) / kPostH);
+    const dim3 grid = image_grid(width, height);
     return launch_by_elem<InterleaveK>(texel_bytes, grid, (hipStream_t)stream, d_src, (int)w4, (int)h4, d_dst,
                                        (int)width, (int)height, "rsd_interleave");
 }
@@ -739,8 +686,7 @@ extern "C" rsd_status rsd_ray_min_max_length(const uint32_t* d_ray_min, const ui
     const uint32_t n = width * height;
     hipLaunchKernelGGL(ray_length_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_ray_min,
                        d_ray_max, n, d_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "ray_length_kernel launch");
+    return launch_status("ray_length_kernel launch");
 }
 
 extern "C" rsd_status rsd_ao_flicker_mask(const float* d_linear_z, const float* d_normal_w, uint32_t width,
@@ -750,11 +696,10 @@ extern "C" rsd_status rsd_ao_flicker_mask(const float* d_linear_z, const float* 
         return RSD_ERR_INVALID_ARG;
     }
     const float isx = 0.5f * (cam->frameWidth / cam->focalLength), isy = 0.5f * (cam->frameHeight / cam->focalLength);
-    const dim3 grid((width + kPostW - 1) / kPostW, (height + kPostH - 1) / kPostH);
-    hipLaunchKernelGGL(flicker_mask_kernel, grid, dim3(kPostW, kPostH), 0, (hipStream_t)stream, d_linear_z,
+    const dim3 grid = image_grid(width, height);
+    hipLaunchKernelGGL(flicker_mask_kernel, grid, image_block(), 0, (hipStream_t)stream, d_linear_z,
                        reinterpret_cast<const float4*>(d_normal_w), (int)width, (int)height, *cam, isx, isy, d_mask);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "flicker_mask_kernel launch");
+    return launch_status("flicker_mask_kernel launch");
 }
 
 extern "C" rsd_status rsd_binary_dilation(const uint8_t* d_in, uint32_t width, uint32_t height, uint32_t op_max,
@@ -763,11 +708,10 @@ extern "C" rsd_status rsd_binary_dilation(const uint8_t* d_in, uint32_t width, u
         set_error("rsd_binary_dilation: invalid argument (op_max 0 = min, 1 = max; no in-place)");
         return RSD_ERR_INVALID_ARG;
     }
-    const dim3 grid((width + kPostW - 1) / kPostW, (height + kPostH - 1) / kPostH);
-    hipLaunchKernelGGL(binary_dilation_kernel, grid, dim3(kPostW, kPostH), 0, (hipStream_t)stream, d_in, (int)width,
+    const dim3 grid = image_grid(width, height);
+    hipLaunchKernelGGL(binary_dilation_kernel, grid, image_block(), 0, (hipStream_t)stream, d_in, (int)width,
                        (int)height, op_max, d_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "binary_dilation_kernel launch");
+    return launch_status("binary_dilation_kernel launch");
 }
 
 extern "C" rsd_status rsd_taa(const float* d_color_in, const float* d_mvec, const float* d_prev_color, uint32_t width,
@@ -789,10 +733,9 @@ extern "C" rsd_status rsd_taa(const float* d_color_in, const float* d_mvec, cons
     a.antiFlicker = anti_flicker;
     a.invW = 1.0f / (float)width;  // TAA.ps.slang:47 invTextureSize
     a.invH = 1.0f / (float)height;
-    const dim3 grid((width + kPostW - 1) / kPostW, (height + kPostH - 1) / kPostH);
-    hipLaunchKernelGGL(taa_kernel, grid, dim3(kPostW, kPostH), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "taa_kernel launch");
+    const dim3 grid = image_grid(width, height);
+    hipLaunchKernelGGL(taa_kernel, grid, image_block(), 0, (hipStream_t)stream, a);
+    return launch_status("taa_kernel launch");
 }
 
 extern "C" rsd_status rsd_temporal_ao(const uint8_t* d_ao_in, const float* d_linear_z, const float* d_mvec,
@@ -821,17 +764,12 @@ extern "C" rsd_status rsd_temporal_ao(const uint8_t* d_ao_in, const float* d_lin
     a.H = (int)height;
     a.g = (int)guard_band;
     for (int i = 0; i < 16; ++i) a.m[i] = prev_view_to_cur_view[i];
-    // GuardBand.cpp:62-63
-    a.uvMinX = ((float)guard_band + 0.5f) / (float)width;
-    a.uvMinY = ((float)guard_band + 0.5f) / (float)height;
-    a.uvMaxX = ((float)width - ((float)guard_band + 0.5f)) / (float)width;
-    a.uvMaxY = ((float)height - ((float)guard_band + 0.5f)) / (float)height;
+    a.uv = guard_uv(width, height, guard_band);
     a.isx = 0.5f * (cam->frameWidth / cam->focalLength);  // TemporalAO.ps.slang:42 imageScale
     a.isy = 0.5f * (cam->frameHeight / cam->focalLength);
-    const dim3 grid((width - 2 * guard_band + kPostW - 1) / kPostW, (height - 2 * guard_band + kPostH - 1) / kPostH);
-    hipLaunchKernelGGL(temporal_ao_kernel, grid, dim3(kPostW, kPostH), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "temporal_ao_kernel launch");
+    const dim3 grid = image_grid(width - 2 * guard_band, height - 2 * guard_band);
+    hipLaunchKernelGGL(temporal_ao_kernel, grid, image_block(), 0, (hipStream_t)stream, a);
+    return launch_status("temporal_ao_kernel launch");
 }
 
 namespace {
@@ -857,10 +795,9 @@ rsd_status motion_vectors_impl(const rsd_camera* cam, const rsd_camera* prev_cam
         a.pV[k] = (float)(prev_cam->V[k] / vv);
         a.pW[k] = (float)(prev_cam->W[k] / ww);
     }
-    const dim3 grid((width + kPostW - 1) / kPostW, (height + kPostH - 1) / kPostH);
-    hipLaunchKernelGGL(motion_vector_kernel, grid, dim3(kPostW, kPostH), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "motion_vector_kernel launch");
+    const dim3 grid = image_grid(width, height);
+    hipLaunchKernelGGL(motion_vector_kernel, grid, image_block(), 0, (hipStream_t)stream, a);
+    return launch_status("motion_vector_kernel launch");
 }
 }  // namespace
 
@@ -908,8 +845,7 @@ extern "C" rsd_status rsd_image_equation_run(const rsd_image_program* prog, cons
     a.W = (int)out->width;
     a.H = (int)out->height;
     a.outFmt = f;
-    const dim3 grid((a.W + kPostW - 1) / kPostW, (a.H + kPostH - 1) / kPostH);
-    hipLaunchKernelGGL(image_equation_kernel, grid, dim3(kPostW, kPostH), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "image_equation_kernel launch");
+    const dim3 grid = image_grid(a.W, a.H);
+    hipLaunchKernelGGL(image_equation_kernel, grid, image_block(), 0, (hipStream_t)stream, a);
+    return launch_status("image_equation_kernel launch");
 }

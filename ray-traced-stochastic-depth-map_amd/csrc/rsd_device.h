@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tex_sample.h"
+
 namespace rsd {
 
 struct f3 { float x, y, z; };
@@ -84,39 +86,31 @@ __device__ __forceinline__ void sd_jitter(uint32_t x, uint32_t y, bool on, float
     jy = kJitter[i + 1];
 }
 
-// Linear filtering of an R32F texture (D3D conventions, 8 sub-texel bits).
+// Linear filtering of an R32F texture by the sampler rule of tex_sample.h.
 // wrap: AddressMode::Wrap (Falcor sampler default) else Clamp.
-__device__ __forceinline__ int tex_addr(int i, int n, bool wrap) {
-    if (wrap) { i %= n; return i < 0 ? i + n : i; }
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
 __device__ __forceinline__ float tex_bilinear(const float* __restrict__ tex, int W, int H, float u, float v, bool wrap) {
-    float x = u * (float)W - 0.5f;
-    float y = v * (float)H - 0.5f;
-    float fx0 = floorf(x), fy0 = floorf(y);
-    float qx = floorf((x - fx0) * 256.0f + 0.5f);
-    float qy = floorf((y - fy0) * 256.0f + 0.5f);
-    int ix = (int)fx0, iy = (int)fy0;
-    if (qx >= 256.0f) { ix += 1; qx = 0.0f; }
-    if (qy >= 256.0f) { iy += 1; qy = 0.0f; }
-    float wx = qx * (1.0f / 256.0f), wy = qy * (1.0f / 256.0f);
-    int x0 = tex_addr(ix, W, wrap), y0 = tex_addr(iy, H, wrap);
+    const TexSplit s = tex_split(W, H, u, v);
+    int x0 = tex_addr(s.ix, W, wrap), y0 = tex_addr(s.iy, H, wrap);
     const float t00 = tex[(size_t)y0 * W + x0];
     // Zero weights: t*(1-0) + t'*0 == t exactly for finite t' (depth texels are finite,
     // DESIGN.md "Numerics"), so the taps with zero weight are not fetched.  Pixel-centre
     // samples (SVAO Init / primary visibility) need 1 fetch instead of 4.
-    if (qx == 0.0f && qy == 0.0f) return t00;
-    int x1 = tex_addr(ix + 1, W, wrap), y1 = tex_addr(iy + 1, H, wrap);
-    if (qy == 0.0f) {
+    if (s.qx == 0.0f && s.qy == 0.0f) return t00;
+    int x1 = tex_addr(s.ix + 1, W, wrap), y1 = tex_addr(s.iy + 1, H, wrap);
+    if (s.qy == 0.0f) {
         const float t10 = tex[(size_t)y0 * W + x1];
-        return t00 * (1.0f - wx) + t10 * wx;
+        return t00 * (1.0f - s.wx) + t10 * s.wx;
     }
     const float t01 = tex[(size_t)y1 * W + x0];
-    if (qx == 0.0f) return t00 * (1.0f - wy) + t01 * wy;
+    if (s.qx == 0.0f) return t00 * (1.0f - s.wy) + t01 * s.wy;
     const float t10 = tex[(size_t)y0 * W + x1], t11 = tex[(size_t)y1 * W + x1];
-    float r0 = t00 * (1.0f - wx) + t10 * wx;
-    float r1 = t01 * (1.0f - wx) + t11 * wx;
-    return r0 * (1.0f - wy) + r1 * wy;
+    return tex_lerp(s, t00, t10, t01, t11);
+}
+// Linear filtering of an R8Unorm texture at a footprint already split and addressed (all four taps): one
+// footprint serves every image sampled at the same place
+__device__ __forceinline__ float unorm8_bilinear_at(const uint8_t* __restrict__ t, const TexSplit& s, const TexTaps& p) {
+    return tex_lerp(s, unorm8_to_float(t[p.t00]), unorm8_to_float(t[p.t10]), unorm8_to_float(t[p.t01]),
+                    unorm8_to_float(t[p.t11]));
 }
 
 // ---- octahedral 2x8 normals: PackedFormats.slang:35-48, MathHelpers.slang:156-194,

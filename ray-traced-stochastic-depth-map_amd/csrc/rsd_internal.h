@@ -128,6 +128,19 @@ struct rsd_scene {
 namespace rsd {
 void set_error(const std::string& msg);
 rsd_status hip_fail(hipError_t e, const char* what);
+// The end of a launcher: the status of the launch just enqueued
+inline rsd_status launch_status(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RSD_OK : hip_fail(e, what);
+}
+
+// The image passes (post.hip, temporal_peel.hip, ao_resolve.hip, hbao.hip) run one lane per pixel in 64 x 4
+// workgroups, so every wave reads whole cache lines of a row: the grid over a w x h rectangle of `layers` slices
+constexpr int kImageBlockW = 64, kImageBlockH = 4;
+inline dim3 image_block() { return dim3(kImageBlockW, kImageBlockH); }
+inline dim3 image_grid(uint32_t w, uint32_t h, uint32_t layers = 1) {
+    return dim3((w + kImageBlockW - 1) / kImageBlockW, (h + kImageBlockH - 1) / kImageBlockH, layers);
+}
 
 // bvh_refit.hip: the launches of one update of a dynamic scene on `st` -- scatter `count` positions into the
 // scene's copy; rewrite the records from that copy and refit every box

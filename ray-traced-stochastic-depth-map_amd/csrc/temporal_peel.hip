@@ -21,8 +21,7 @@
 namespace rsd {
 namespace {
 
-constexpr int kPeelW = 64, kPeelH = 4;  // post.hip's block shape
-constexpr int kClipRounds = 8;          // :61 "max number of iterations = 4"; capped, never unbounded
+constexpr int kClipRounds = 8;  // :61 "max number of iterations = 4"; capped, never unbounded
 
 struct PeelArgs {
     const float* z;
@@ -54,7 +53,7 @@ __device__ __forceinline__ float border_texel(const float* __restrict__ t, int W
     return t[(size_t)(int)cy * W + (int)cx];
 }
 
-// GetRectifiedDepth (:209-235)
+// GetRectifiedDepth (:209-235).  Not tex_sample.h's sampler: the shader's own gather, unquantised fraction, Border 0
 __device__ __forceinline__ float rectified_depth(const PeelArgs& a, float u, float v, float farLimit) {
     const float px = u * (float)a.W - 0.5f, py = v * (float)a.H - 0.5f;
     const float fx = floorf(px), fy = floorf(py);
@@ -76,8 +75,8 @@ __device__ __forceinline__ float rectified_depth(const PeelArgs& a, float u, flo
     return 1.0f / (w0 * (1.0f / n0) + w1 * (1.0f / n1) + w2 * (1.0f / n2) + w3 * (1.0f / n3));  // zlerp(n, w)
 }
 
-__global__ void __launch_bounds__(kPeelW * kPeelH) temporal_peel_kernel(PeelArgs a) {
-    const int x = (int)(blockIdx.x * kPeelW + threadIdx.x), y = (int)(blockIdx.y * kPeelH + threadIdx.y);
+__global__ void __launch_bounds__(kImageBlockW * kImageBlockH) temporal_peel_kernel(PeelArgs a) {
+    const int x = (int)(blockIdx.x * kImageBlockW + threadIdx.x), y = (int)(blockIdx.y * kImageBlockH + threadIdx.y);
     if (x >= a.W || y >= a.H) return;
     const size_t o = (size_t)y * a.W + x;
     const float tu = ((float)x + 0.5f) / (float)a.W, tv = ((float)y + 0.5f) / (float)a.H;  // texC
@@ -204,8 +203,6 @@ extern "C" rsd_status rsd_temporal_depth_peel(const float* d_linear_z, const flo
     a.farZ = cam->farZ;
     a.sep = min_separation;
     a.maxIter = (int)max_iterations;
-    const dim3 grid((width + kPeelW - 1) / kPeelW, (height + kPeelH - 1) / kPeelH);
-    hipLaunchKernelGGL(temporal_peel_kernel, grid, dim3(kPeelW, kPeelH), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? RSD_OK : hip_fail(e, "temporal_peel_kernel launch");
+    hipLaunchKernelGGL(temporal_peel_kernel, image_grid(width, height), image_block(), 0, (hipStream_t)stream, a);
+    return launch_status("temporal_peel_kernel launch");
 }
