@@ -374,6 +374,27 @@ typedef struct {
 } rsd_scene_rig_info;
 rsd_status rsd_scene_rig_info_get(const rsd_scene* scene, rsd_scene_rig_info* out);
 
+/* --- motion tracking: the previous positions of a dynamic scene (DESIGN.md 4 "Motion vectors of moving
+ * geometry") ---
+ * Opt-in: a scene that never calls rsd_scene_track_motion allocates, behaves and reports as before.
+ * Track the motion of a scene of rsd_scene_upload_dynamic (RSD_ERR_INVALID_ARG on any other scene): allocate one
+ * float3[vertex_count] buffer of previous positions and fill it from the scene's current positions.
+ * Synchronous like rsd_scene_attach_rig (waits for the device); a second call does nothing. */
+rsd_status rsd_scene_track_motion(rsd_scene* scene);
+/* previous positions <- current positions.  Stream-ordered, no host wait, no allocation: one copy kernel on
+ * `stream`, under the updates' single-stream ordering contract.  The updates never snapshot on their own: the
+ * previous positions are the positions at the last rsd_scene_motion_begin_frame (or at rsd_scene_track_motion),
+ * however many rsd_scene_update_* calls ran since.  When no update was enqueued since the last snapshot the
+ * buffers are already equal and the call enqueues nothing.  RSD_ERR_INVALID_ARG on a scene that is not tracked. */
+rsd_status rsd_scene_motion_begin_frame(rsd_scene* scene, rsd_stream stream);
+typedef struct {
+    uint32_t tracked;       /* 1: rsd_scene_track_motion was called */
+    uint32_t reserved;
+    uint64_t snapshots;     /* copies rsd_scene_motion_begin_frame actually enqueued */
+    uint64_t motion_bytes;  /* device bytes of the previous positions (not part of dynamic_bytes) */
+} rsd_scene_motion_info;
+rsd_status rsd_scene_motion_info_get(const rsd_scene* scene, rsd_scene_motion_info* out);
+
 /* --- host helpers (no GPU work) ---------------------------------------------------- */
 /* RAY_CONE_SPREAD of the SD pass (StochasticDepthMapRT.cpp:266-267): Camera::
  * computeScreenSpacePixelSpreadAngle(height) (Camera.cpp:296-301) with the fovY of the 24 mm
@@ -407,6 +428,25 @@ rsd_status rsd_gbuffer_raster(rsd_scene* scene, const rsd_camera* cam, uint32_t 
 rsd_status rsd_gbuffer_world(rsd_scene* scene, const rsd_camera* cam, uint32_t width, uint32_t height,
                              uint32_t cull_mode, float* d_depth, float* d_normal_w, float* d_pos_w,
                              rsd_stream stream);
+/* rsd_gbuffer_world (d_pos_w may be NULL here) plus the motion vectors of moving geometry, in one launch and
+ * one BVH walk per pixel: d_depth, d_normal_w and d_pos_w get rsd_gbuffer_world's bytes; d_mvec (RG32F) the
+ * screen-space motion vector GBufferRaster.mvec; d_mvec_w (RGBA32F, may be NULL) the world-space one.  The scene
+ * must track motion (rsd_scene_track_motion): RSD_ERR_INVALID_ARG "motion is not tracked" otherwise.
+ * Definition (librsd's; every product and sum rounded to float32 on its own, no FMA).  For the winning hit
+ * (the closest (t, prim) after culling and the alpha test) with record vertices v0, v1, v2, primitive id prim
+ * and the barycentrics bu, bv of the triangle test (bu weighs v1, bv weighs v2):
+ *   i_j = indices[3 prim + j]        d_j = prev_positions[i_j] - v_j   (per component; v_j: the current bits)
+ *   b0 = (1 - bu) - bv               D = (b0 d0 + bu d1) + bv d2
+ *   P = o + d t  (exactly posW)      P_prev = P + D
+ *   rel = P_prev - prev_cam.posW;  pa, pb, pw = dot(rel, U/|U|^2), dot(rel, V/|V|^2), dot(rel, W/|W|^2) of
+ *   prev_cam (the three vectors evaluated in double and rounded once; each dot (x + y) + z)
+ *   mvec = ((pa / pw + 1) 0.5 - u, (1 - pb / pw) 0.5 - v) when pw > 0, else (2, 2);  u, v: the pixel centre
+ *   mvecW = (D, 0)
+ * A miss gives mvec = (0, 0) and mvecW = 0.  A vertex that did not move since the last snapshot has d_j = 0
+ * exactly, so static geometry gets D = +0 and the camera's term alone, computed from the hit itself. */
+rsd_status rsd_gbuffer_motion(rsd_scene* scene, const rsd_camera* cam, const rsd_camera* prev_cam, uint32_t width,
+                              uint32_t height, uint32_t cull_mode, float* d_depth, float* d_normal_w, float* d_pos_w,
+                              float* d_mvec, float* d_mvec_w, rsd_stream stream);
 
 /* --- RTAO: ray-traced ambient occlusion (RenderPasses/RTAO; the ground truth screen-space AO is judged by) ---
  * Per pixel of the world-position G-buffer, spp cosine-distributed hemisphere rays about the face normal

@@ -54,8 +54,12 @@ rsd_status rsd_graph_mark_output(rsd_graph* g, const char* name);
 rsd_status rsd_graph_set_scene(rsd_graph* g, rsd_scene* scene, const rsd_camera* cam);
 /* Moved geometry (rsd.h rsd_scene_update_positions) for the graph's scene, which the application uploaded with
  * rsd_scene_upload_dynamic before rsd_graph_set_scene: enqueued on `stream`, so the next rsd_graph_execute on
- * that stream renders the moved scene.  Passes that keep history (TemporalAO, TemporalDepthPeel, the G-buffer's
- * motion vectors) know the camera's motion only, not the geometry's. */
+ * that stream renders the moved scene.  GBufferRaster.mvec follows the geometry when the scene tracks motion
+ * (rsd.h rsd_scene_track_motion): the pass then renders with rsd_gbuffer_motion and snapshots the positions
+ * after it ran (rsd_scene_motion_begin_frame), so the updates enqueued before the next execute are measured
+ * against this frame; TemporalAO and TAA reproject with that mvec.  On a scene that does not track motion mvec
+ * knows the camera's motion only.  TemporalDepthPeel does not read mvec and TemporalAO's depth-rejection test
+ * transforms the previous depth with the camera alone: those know the camera's motion only. */
 rsd_status rsd_graph_update_scene_positions(rsd_graph* g, const float* positions, uint32_t vertex_count,
                                             uint32_t positions_on_device, rsd_stream stream);
 /* The same for a pose of the scene's rig (rsd.h rsd_scene_update_pose; the rig was attached to the scene with

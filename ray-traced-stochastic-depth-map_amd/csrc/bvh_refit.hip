@@ -1,6 +1,9 @@
 // bvh_refit.hip -- dynamic scenes: rewrite the triangle records from moved vertices and refit the boxes of
 // the existing 4-wide tree on the GPU, in stream order (rsd_scene_update_positions / _subset).
 //
+// Also here: motion_snapshot_kernel, the copy of the positions into the previous positions of a scene that
+// tracks motion (rsd_scene_motion_begin_frame).
+//
 // Two launches.  refit_records_kernel: one lane per triangle record gathers its three vertices through the
 // index buffer and stores the nine position words; the prim / flags / pad words are never written.
 // refit_boxes_kernel: one launch, bottom-up.  One lane per wide node computes the boxes of its LEAF children
@@ -46,6 +49,22 @@ __global__ __launch_bounds__(kRefitBlock) void refit_scatter_kernel(uint32_t* __
     const uint32_t v = ids[i];
     if (v >= nv) return;  // an id outside the scene moves nothing
     for (int k = 0; k < 3; ++k) pos[3 * (size_t)v + k] = src[3 * (size_t)i + k];
+}
+
+// Motion tracking (rsd_scene_motion_begin_frame): dst[0, n) <- src[0, n) in dwords.  Lanes [0, nvec) move one
+// 16-byte vector each (nvec = n / 4 when both buffers are 16-byte aligned, the launcher's decision, else 0), the
+// lanes after them one dword each of the tail [4 nvec, n).  A kernel, not a copy call: it sits in stream
+// order with the refit launches and shows by name in a kernel trace.
+__global__ __launch_bounds__(kRefitBlock) void motion_snapshot_kernel(uint32_t* __restrict__ dst,
+                                                                      const uint32_t* __restrict__ src, uint32_t n,
+                                                                      uint32_t nvec) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i < nvec) {
+        reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+        return;
+    }
+    const uint32_t k = 4u * nvec + (i - nvec);  // nvec <= n / 4 < 2^30: no wrap
+    if (k < n) dst[k] = src[k];
 }
 
 __global__ __launch_bounds__(kRefitBlock) void refit_records_kernel(uint32_t* __restrict__ recs, uint32_t nt,
@@ -133,6 +152,24 @@ rsd_status refit_scatter_enqueue(rsd_scene* s, const uint32_t* d_ids, const floa
                        reinterpret_cast<const uint32_t*>(d_positions), count);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? RSD_OK : hip_fail(e, "refit_scatter_kernel launch");
+}
+
+rsd_status motion_snapshot_enqueue(rsd_scene* s, hipStream_t st) {
+    const uint64_t n64 = 3 * (uint64_t)s->vertex_count;
+    if (!n64) return RSD_OK;
+    if (n64 > 0xffffff00ull) {  // the lane count below, rounded up to blocks, stays in 32 bits
+        set_error("rsd_scene_motion_begin_frame: too many vertices for one launch");
+        return RSD_ERR_UNSUPPORTED;
+    }
+    const uint32_t n = (uint32_t)n64;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(s->dyn.prev_positions);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(s->dyn.positions);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
+    const uint32_t nvec = aligned ? n / 4u : 0u;
+    const uint32_t lanes = nvec + (n - 4u * nvec);
+    hipLaunchKernelGGL(motion_snapshot_kernel, dim3((lanes + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st,
+                       dst, src, n, nvec);
+    return launch_status("motion_snapshot_kernel launch");
 }
 
 rsd_status refit_enqueue(rsd_scene* s, hipStream_t st) {

@@ -4,7 +4,9 @@
 //   GuardBand             GuardBand.cpp:38-64        dict["guardBand"]
 //   GBufferRaster         GBufferRaster.cpp:86-230   depth + faceNormalW (rsd_gbuffer_raster),
 //                                                    mvec when connected (rsd_motion_vectors_raster),
-//                                                    posW when connected (rsd_gbuffer_world)
+//                                                    posW when connected (rsd_gbuffer_world); on a scene
+//                                                    that tracks motion, mvec / mvecW of the moving
+//                                                    geometry (rsd_gbuffer_motion, then the snapshot)
 //   LinearizeDepth        LinearizeDepth.cpp:73-96   rsd_linearize_depth
 //   CompressNormals       CompressNormals.cpp:70-96  rsd_compress_normals (viewSpace, 16 bit)
 //   DepthPeeling          DepthPeeling.cpp:54-115    rsd_depth_peel (DualDepth's second layer)
@@ -154,6 +156,10 @@ public:
         Field& pw = r.addOutput("posW", "Position in world space (xyz, w = 1; background 0)");
         pw.format = Format::RGBA32Float;
         pw.optional = true;  // GBuffer.cpp:42: likewise
+        // librsd's own channel (GBufferRT's mvecW): the hit's world-space motion, on a scene that tracks motion
+        Field& mw = r.addOutput("mvecW", "Motion vector in world space (xyz, w = 0)");
+        mw.format = Format::RGBA32Float;
+        mw.optional = true;
         return r;
     }
     void setScene(Context&, const SceneRef* s) override {
@@ -164,9 +170,35 @@ public:
         if (!scene_) return;  // GBufferRaster.cpp:157 no scene -> outputs stay cleared
         Texture* d = rd["depth"];
         Texture* n = rd["faceNormalW"];
-        if (Texture* pw = rd["posW"]) {  // something reads posW: the same kernel writes it too
-            if (pw->format != Format::RGBA32Float || pw->width != d->width || pw->height != d->height)
-                throw Unsupported("GBufferRaster: posW must be RGBA32Float at the depth size");
+        Texture* pw = rd["posW"];
+        if (pw && (pw->format != Format::RGBA32Float || pw->width != d->width || pw->height != d->height))
+            throw Unsupported("GBufferRaster: posW must be RGBA32Float at the depth size");
+        rsd_scene_motion_info motion{};
+        check(rsd_scene_motion_info_get(scene_->scene, &motion), "GBufferRaster");
+        Texture* mw = rd["mvecW"];
+        if (mw && !motion.tracked)
+            throw Unsupported("GBufferRaster: mvecW needs a scene that tracks motion (rsd_scene_track_motion)");
+        if (mw && (mw->format != Format::RGBA32Float || mw->width != d->width || mw->height != d->height))
+            throw Unsupported("GBufferRaster: mvecW must be RGBA32Float at the depth size");
+        if (motion.tracked && (rd["mvec"] || mw)) {
+            // moving geometry: one launch writes depth, normal, posW and the motion vectors of the hit, against the
+            // positions of the previous execute's snapshot and the previous execute's camera; then the snapshot,
+            // so that updates enqueued before the next execute are measured against this frame
+            Texture* mv = rd["mvec"];
+            if (mv && (mv->format != Format::RG32Float || mv->width != d->width || mv->height != d->height))
+                throw Unsupported("GBufferRaster: mvec must be RG32Float at the depth size");
+            if (!mv) throw Unsupported("GBufferRaster: mvecW is written with mvec; connect mvec too");
+            const rsd_camera prev = hasPrev_ ? prevCam_ : scene_->camera;
+            prevCam_ = scene_->camera;
+            hasPrev_ = true;
+            check(rsd_gbuffer_motion(scene_->scene, &scene_->camera, &prev, d->width, d->height, cull_, (float*)d->ptr,
+                                     (float*)n->ptr, pw ? (float*)pw->ptr : nullptr, (float*)mv->ptr,
+                                     mw ? (float*)mw->ptr : nullptr, ctx.stream),
+                  "GBufferRaster");
+            check(rsd_scene_motion_begin_frame(scene_->scene, ctx.stream), "GBufferRaster");
+            return;
+        }
+        if (pw) {  // something reads posW: the same kernel writes it too
             check(rsd_gbuffer_world(scene_->scene, &scene_->camera, d->width, d->height, cull_, (float*)d->ptr,
                                     (float*)n->ptr, (float*)pw->ptr, ctx.stream),
                   "GBufferRaster");

@@ -787,14 +787,7 @@ rsd_status motion_vectors_impl(const rsd_camera* cam, const rsd_camera* prev_cam
     a.mvec = reinterpret_cast<float2*>(d_mvec);
     a.W = (int)width;
     a.H = (int)height;
-    auto dot3 = [](const float* p, const float* q) { return (double)p[0] * q[0] + (double)p[1] * q[1] + (double)p[2] * q[2]; };
-    const double uu = dot3(prev_cam->U, prev_cam->U), vv = dot3(prev_cam->V, prev_cam->V),
-                 ww = dot3(prev_cam->W, prev_cam->W);
-    for (int k = 0; k < 3; ++k) {
-        a.pU[k] = (float)(prev_cam->U[k] / uu);
-        a.pV[k] = (float)(prev_cam->V[k] / vv);
-        a.pW[k] = (float)(prev_cam->W[k] / ww);
-    }
+    mvec_prev_axes(*prev_cam, a.pU, a.pV, a.pW);
     const dim3 grid = image_grid(width, height);
     hipLaunchKernelGGL(motion_vector_kernel, grid, image_block(), 0, (hipStream_t)stream, a);
     return launch_status("motion_vector_kernel launch");

@@ -611,6 +611,54 @@ extern "C" rsd_status rsd_scene_rig_info_get(const rsd_scene* s, rsd_scene_rig_i
     return RSD_OK;
 }
 
+extern "C" rsd_status rsd_scene_track_motion(rsd_scene* s) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_track_motion"); st != RSD_OK) return st;
+    if (s->dyn.prev_positions) return RSD_OK;
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    // synchronous: updates enqueued so far have run before the positions are copied
+    RSD_HIP(hipDeviceSynchronize());
+    const size_t bytes = 12 * (size_t)s->vertex_count;
+    float* d = nullptr;
+    hipError_t e = hipMalloc(&d, bytes ? bytes : 256);
+    if (e == hipSuccess && bytes) e = hipMemcpy(d, s->dyn.positions, bytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return rsd::hip_fail(e, "rsd_scene_track_motion");
+    }
+    s->dyn.prev_positions = d;
+    s->motion_bytes = bytes ? bytes : 256;
+    s->device_bytes += s->motion_bytes;
+    s->motion_seen_updates = s->updates;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_scene_motion_begin_frame(rsd_scene* s, rsd_stream stream) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_motion_begin_frame"); st != RSD_OK) return st;
+    if (!s->dyn.prev_positions) {
+        set_error("rsd_scene_motion_begin_frame: motion is not tracked (rsd_scene_track_motion)");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (s->motion_seen_updates == s->updates) return RSD_OK;  // no update since the last snapshot: already equal
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    if (rsd_status st = rsd::motion_snapshot_enqueue(s, (hipStream_t)stream); st != RSD_OK) return st;
+    s->motion_seen_updates = s->updates;
+    ++s->motion_snapshots;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_scene_motion_info_get(const rsd_scene* s, rsd_scene_motion_info* out) {
+    if (!s || !out) {
+        set_error("rsd_scene_motion_info_get: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    out->tracked = s->dyn.prev_positions ? 1u : 0u;
+    out->reserved = 0;
+    out->snapshots = s->motion_snapshots;
+    out->motion_bytes = s->motion_bytes;
+    return RSD_OK;
+}
+
 extern "C" rsd_status rsd_scene_rebuild_entry_grid(rsd_scene* s) {
     if (!s) {
         set_error("rsd_scene_rebuild_entry_grid: null scene");
@@ -731,6 +779,7 @@ extern "C" void rsd_scene_release(rsd_scene* s) {
     (void)hipFree(s->d_entry);
     (void)hipFree(s->d_rtao_table);
     (void)hipFree(s->d_dyn);
+    (void)hipFree(s->dyn.prev_positions);
     (void)hipFree(s->d_rig);
     delete s;
 }

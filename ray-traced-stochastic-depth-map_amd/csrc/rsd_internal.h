@@ -72,6 +72,9 @@ struct DynamicData {
     uint32_t* inner = nullptr;    // per wide node: its count of inner children
     uint32_t* arrive = nullptr;   // per wide node: inner children arrived in this refit (zero between refits)
     uint32_t* tight = nullptr;    // per wide node: its tight box as keys, lo[3] hi[3] (bvh_refit.h)
+    // motion tracking (rsd_scene_track_motion): float3[vertex_count], the positions at the last
+    // rsd_scene_motion_begin_frame; an allocation of its own (rsd_scene.motion_bytes), null when not tracked
+    float* prev_positions = nullptr;
 };
 
 // The rig of a dynamic scene (rsd_scene_attach_rig, csrc/skinning.hip): pointers into rsd_scene.d_rig, one
@@ -116,6 +119,9 @@ struct rsd_scene {
     uint32_t vertex_count = 0;
     uint64_t dyn_bytes = 0;
     uint64_t updates = 0;        // rsd_scene_update_* calls enqueued so far
+    uint64_t motion_bytes = 0;       // dyn.prev_positions' allocation
+    uint64_t motion_snapshots = 0;   // copies rsd_scene_motion_begin_frame enqueued
+    uint64_t motion_seen_updates = 0;  // `updates` at the last snapshot: equal = prev_positions holds the positions
     // an update moved geometry since the entry grid was built: traces pass no table (the root-start path)
     // until rsd_scene_rebuild_entry_grid
     bool entry_stale = false;
@@ -147,8 +153,22 @@ inline dim3 image_grid(uint32_t w, uint32_t h, uint32_t layers = 1) {
 rsd_status refit_scatter_enqueue(rsd_scene* s, const uint32_t* d_ids, const float* d_positions, uint32_t count,
                                  hipStream_t st);
 rsd_status refit_enqueue(rsd_scene* s, hipStream_t st);
+// prev_positions <- positions of a scene that tracks motion, one launch on `st`
+rsd_status motion_snapshot_enqueue(rsd_scene* s, hipStream_t st);
 // skinning.hip: pose the rig's vertices into the scene's position copy from `d_matrices` (float[matrix_count][12])
 rsd_status pose_enqueue(rsd_scene* s, const float* d_matrices, hipStream_t st);
+
+// The previous camera's terms of the motion-vector projection (post.hip motion_vector_kernel, gbuffer_motion.hip):
+// U / |U|^2, V / |V|^2, W / |W|^2, evaluated in double and rounded once
+inline void mvec_prev_axes(const rsd_camera& prev, float pU[3], float pV[3], float pW[3]) {
+    auto dot3 = [](const float* p, const float* q) { return (double)p[0] * q[0] + (double)p[1] * q[1] + (double)p[2] * q[2]; };
+    const double uu = dot3(prev.U, prev.U), vv = dot3(prev.V, prev.V), ww = dot3(prev.W, prev.W);
+    for (int k = 0; k < 3; ++k) {
+        pU[k] = (float)(prev.U[k] / uu);
+        pV[k] = (float)(prev.V[k] / vv);
+        pW[k] = (float)(prev.W[k] / ww);
+    }
+}
 
 // sd_trace.hip (host code): the stratified coverage-mask tables of N samples on HIP device `dev` (indices [N + 1], look-up
 // table [2^N]), uploaded once per (device, N) and never freed; shared by the SD trace and sd_raster.hip

@@ -72,6 +72,11 @@ class SceneRigInfo(C.Structure):  # rsd_scene_rig_info
                 ("reserved", C.c_uint32), ("rig_bytes", C.c_uint64)]
 
 
+class SceneMotionInfo(C.Structure):  # rsd_scene_motion_info
+    _fields_ = [("tracked", C.c_uint32), ("reserved", C.c_uint32), ("snapshots", C.c_uint64),
+                ("motion_bytes", C.c_uint64)]
+
+
 class Camera(C.Structure):
     _fields_ = [("posW", C.c_float * 3), ("nearZ", C.c_float),
                 ("U", C.c_float * 3), ("farZ", C.c_float),
@@ -288,7 +293,8 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_rtao", "rsd_rtao_sample_table", "rsd_rtao_ray_t_max", "rsd_rtao_pack", "rsd_hbao",
            "rsd_hbao_noise_table", "rsd_sd_raster", "rsd_scene_upload_dynamic", "rsd_scene_update_positions",
            "rsd_scene_update_subset", "rsd_scene_rebuild_entry_grid", "rsd_scene_dynamic_info_get", "rsd_bvh_refit",
-           "rsd_scene_attach_rig", "rsd_scene_update_pose", "rsd_scene_rig_info_get"]
+           "rsd_scene_attach_rig", "rsd_scene_update_pose", "rsd_scene_rig_info_get", "rsd_scene_track_motion",
+           "rsd_scene_motion_begin_frame", "rsd_scene_motion_info_get", "rsd_gbuffer_motion"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -360,6 +366,12 @@ def lib():
         L.rsd_scene_update_pose.argtypes = [vp, vp, u32, u32, vp]
         L.rsd_scene_rig_info_get.restype = st
         L.rsd_scene_rig_info_get.argtypes = [vp, C.POINTER(SceneRigInfo)]
+        L.rsd_scene_track_motion.restype = st
+        L.rsd_scene_track_motion.argtypes = [vp]
+        L.rsd_scene_motion_begin_frame.restype = st
+        L.rsd_scene_motion_begin_frame.argtypes = [vp, vp]
+        L.rsd_scene_motion_info_get.restype = st
+        L.rsd_scene_motion_info_get.argtypes = [vp, C.POINTER(SceneMotionInfo)]
         L.rsd_bvh_refit.restype = st
         L.rsd_bvh_refit.argtypes = [vp, C.c_uint64, u32, vp, u32, vp, u32, vp]
         L.rsd_ray_cone_spread.restype = f32
@@ -462,6 +474,8 @@ def lib():
         L.rsd_gbuffer_raster.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, vp, vp]
         L.rsd_gbuffer_world.restype = st
         L.rsd_gbuffer_world.argtypes = [vp, C.POINTER(Camera), u32, u32, u32, vp, vp, vp, vp]
+        L.rsd_gbuffer_motion.restype = st
+        L.rsd_gbuffer_motion.argtypes = [vp, C.POINTER(Camera), C.POINTER(Camera), u32, u32, u32, vp, vp, vp, vp, vp, vp]
         L.rsd_rtao.restype = st
         L.rsd_rtao.argtypes = [vp, C.POINTER(RTAOParams), u32, u32, vp, vp, u32, vp, vp, vp, vp]
         L.rsd_rtao_sample_table.restype = st

@@ -213,9 +213,12 @@ def host_bvh_refit(bvh, tri_offset: int, indices, positions):
 
 
 class GpuScene:
-    def __init__(self, dev: Device, scene: Scene, dynamic: bool = False):
+    def __init__(self, dev: Device, scene: Scene, dynamic: bool = False, motion: bool = False):
         """dynamic=True: rsd_scene_upload_dynamic -- the scene's vertices can move (update_positions,
-        update_subset), its BVH being refitted on the GPU."""
+        update_subset), its BVH being refitted on the GPU.  motion=True (with dynamic=True): the scene also keeps
+        its previous positions (track_motion), for the motion vectors of moving geometry."""
+        if motion and not dynamic:
+            raise ValueError("GpuScene: motion=True needs dynamic=True")
         desc = abi.SceneDesc(scene.positions.ctypes.data, scene.positions.shape[0], scene.indices.ctypes.data,
                              scene.indices.shape[0], scene.flags.ctypes.data)
         h = C.c_void_p()
@@ -238,6 +241,8 @@ class GpuScene:
         self.rig = None
         if dynamic and getattr(scene, "rig", None) is not None:
             self.attach_rig(scene.rig)
+        if motion:
+            self.track_motion()
         self.info = abi.SceneInfo()
         abi.check(abi.lib().rsd_scene_info_get(h, C.byref(self.info)), "rsd_scene_info_get")
 
@@ -328,6 +333,22 @@ class GpuScene:
         abi.check(abi.lib().rsd_scene_rig_info_get(self.h, C.byref(d)), "rsd_scene_rig_info_get")
         return d
 
+    def track_motion(self):
+        """rsd_scene_track_motion: keep the previous positions of this dynamic scene (one float3 per vertex, filled
+        from the current positions).  Synchronous; a second call does nothing."""
+        abi.check(abi.lib().rsd_scene_track_motion(self.h), "rsd_scene_track_motion")
+
+    def begin_frame(self, stream=None):
+        """rsd_scene_motion_begin_frame: previous positions <- current positions, on the stream.  The updates never
+        snapshot on their own: motion is measured against the positions at the last begin_frame, however many
+        updates ran since.  Enqueues nothing when no update ran since the last snapshot."""
+        abi.check(abi.lib().rsd_scene_motion_begin_frame(self.h, self._stream(stream)), "rsd_scene_motion_begin_frame")
+
+    def motion_info(self) -> abi.SceneMotionInfo:
+        d = abi.SceneMotionInfo()
+        abi.check(abi.lib().rsd_scene_motion_info_get(self.h, C.byref(d)), "rsd_scene_motion_info_get")
+        return d
+
     def rebuild_entry_grid(self):
         """Make the segment entry grid current again after updates (rsd_scene_rebuild_entry_grid; synchronous)."""
         abi.check(abi.lib().rsd_scene_rebuild_entry_grid(self.h), "rsd_scene_rebuild_entry_grid")
@@ -355,8 +376,9 @@ class Renderer:
     """Owns the frame buffers of one config on one GPU and runs the hot path."""
 
     def __init__(self, scene: Scene, cfg: FrameConfig, device: int = 0, gpu_scene: GpuScene | None = None,
-                 dev: Device | None = None, dynamic: bool = False):
-        """dynamic=True uploads the scene as a dynamic one (GpuScene(dynamic=True)): update_positions() moves it."""
+                 dev: Device | None = None, dynamic: bool = False, motion: bool = False):
+        """dynamic=True uploads the scene as a dynamic one (GpuScene(dynamic=True)): update_positions() moves it.
+        motion=True (with dynamic=True) also tracks its motion (GpuScene(motion=True)): gbuffer_motion()."""
         import torch
         global _raw_stream
         self.torch = torch
@@ -366,7 +388,7 @@ class Renderer:
         self.scene = scene
         self.dev = dev or Device(device)
         torch.cuda.set_device(self.dev.index)
-        self.gscene = gpu_scene or GpuScene(self.dev, scene, dynamic=dynamic)
+        self.gscene = gpu_scene or GpuScene(self.dev, scene, dynamic=dynamic, motion=motion)
         self.cam = make_camera(scene, cfg)
         self.vao, self.sd_w, self.sd_h = make_vao(cfg)
         self.sdp = sd_params(cfg, self.vao.sdGuard)
@@ -495,6 +517,23 @@ class Renderer:
         abi.check(abi.lib().rsd_gbuffer(self.gscene.h, C.byref(self.cam), self.cfg.fb_w, self.cfg.fb_h,
                                         self.cfg.cull_mode, _ptr(self.depth), _ptr(self.normals), self.stream),
                   "rsd_gbuffer")
+
+    def gbuffer_motion(self, prev_cam: abi.Camera, pos_w: bool = True, mvec_w: bool = True):
+        """The raster-style G-buffer of this renderer's frame with the motion vectors of moving geometry
+        (rsd_gbuffer_motion; the scene tracks motion: Renderer(motion=True) or GpuScene.track_motion): one launch.
+        prev_cam: the previous frame's camera.  The motion is measured against the scene's positions at the last
+        GpuScene.begin_frame; this call does not snapshot.  Returns a dict of float32 tensors of the frame size:
+        depth (non-linear), normal_w (x 4), pos_w (x 4, or None), mvec (x 2, uv units), mvec_w (x 4, or None)."""
+        t, W, H = self.torch, self.cfg.fb_w, self.cfg.fb_h
+        f32 = dict(dtype=t.float32, device=self.depth.device)
+        out = {"depth": t.empty((H, W), **f32), "normal_w": t.empty((H, W, 4), **f32),
+               "pos_w": t.empty((H, W, 4), **f32) if pos_w else None, "mvec": t.empty((H, W, 2), **f32),
+               "mvec_w": t.empty((H, W, 4), **f32) if mvec_w else None}
+        abi.check(abi.lib().rsd_gbuffer_motion(self.gscene.h, C.byref(self.cam), C.byref(prev_cam), W, H,
+                                               self.cfg.cull_mode, _ptr(out["depth"]), _ptr(out["normal_w"]),
+                                               _ptr(out["pos_w"]), _ptr(out["mvec"]), _ptr(out["mvec_w"]), self.stream),
+                  "rsd_gbuffer_motion")
+        return out
 
     def depth_peel(self, min_separation: float, cull_mode: int | None = None):
         """Fill self.depth2, the second depth layer of the DualDepth primary mode, from self.depth: per

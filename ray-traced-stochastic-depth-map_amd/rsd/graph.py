@@ -98,7 +98,9 @@ class RenderGraph:
 
     # -- application surface
     def set_scene(self, scene_handle, camera: abi.Camera, rig=None):
-        """rig: the rsd.animation.Rig attached to the scene (GpuScene.rig), for animate(t)."""
+        """rig: the rsd.animation.Rig attached to the scene (GpuScene.rig), for animate(t).  When the scene tracks its
+        motion (GpuScene(dynamic=True, motion=True)), GBufferRaster.mvec follows the moving geometry and the pass
+        snapshots the positions after each execute; nothing else is needed here."""
         abi.check(self._L.rsd_graph_set_scene(self._h, scene_handle, C.byref(camera)), "set_scene")
         if rig is not None:
             self._rig = rig

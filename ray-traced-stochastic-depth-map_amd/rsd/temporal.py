@@ -59,6 +59,27 @@ def motion_vectors(cam: abi.Camera, prev_cam: abi.Camera, linear_z, out=None, st
     return out
 
 
+def motion_vectors_scene(gpu_scene, cam: abi.Camera, prev_cam: abi.Camera, width: int, height: int,
+                         cull_mode: int = abi.CULL_BACK, pos_w: bool = False, mvec_w: bool = True, stream=None):
+    """GBufferRaster.mvec of a scene whose geometry moves (rsd_gbuffer_motion), for callers outside a graph:
+    gpu_scene is a GpuScene(dynamic=True, motion=True); the motion is the camera's (cam after prev_cam) plus the
+    geometry's since the scene's last begin_frame().  One launch that also renders the raster-style G-buffer.
+    Returns a dict of float32 tensors: depth (H x W, non-linear), normal_w (x 4), pos_w (x 4, or None),
+    mvec (x 2, uv units), mvec_w (x 4: the hit's world-space motion, or None).  The caller decides when the
+    frame ends: gpu_scene.begin_frame()."""
+    import torch
+    H, W = int(height), int(width)
+    f32 = dict(dtype=torch.float32, device=torch.device("cuda", gpu_scene.dev.index))
+    out = {"depth": torch.empty((H, W), **f32), "normal_w": torch.empty((H, W, 4), **f32),
+           "pos_w": torch.empty((H, W, 4), **f32) if pos_w else None, "mvec": torch.empty((H, W, 2), **f32),
+           "mvec_w": torch.empty((H, W, 4), **f32) if mvec_w else None}
+    s = stream if stream is not None else C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    abi.check(abi.lib().rsd_gbuffer_motion(gpu_scene.h, C.byref(cam), C.byref(prev_cam), W, H, int(cull_mode),
+                                           _ptr(out["depth"]), _ptr(out["normal_w"]), _ptr(out["pos_w"]),
+                                           _ptr(out["mvec"]), _ptr(out["mvec_w"]), s), "rsd_gbuffer_motion")
+    return out
+
+
 class TemporalAO:
     """One TemporalAO pass instance: keeps the previous frame's depth, AO and history count."""
 
