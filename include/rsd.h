@@ -374,6 +374,46 @@ typedef struct {
 } rsd_scene_rig_info;
 rsd_status rsd_scene_rig_info_get(const rsd_scene* scene, rsd_scene_rig_info* out);
 
+/* --- morph targets (blend shapes) of a rig (DESIGN.md 4 "glTF and morph targets") ----------------
+ * A morph table gives each rig vertex a run of (weight id, delta) entries, in CSR form over the rig's vertices
+ * (entry e of rig vertex i: offsets[i] <= e < offsets[i + 1]).  A pose with a weight table then starts from
+ *   p = rest[i];   for e ascending, for c in x, y, z:   p.c = p.c + (w[weight_ids[e]] * deltas[e].c)
+ * -- the product rounded to float32, then the sum (no FMA), every entry evaluated, a weight of 0 included --
+ * and rsd_scene_update_pose's blend and transform run on p in place of the rest position.  A vertex without
+ * entries gets the bits of rsd_scene_update_pose.  All pointers are host memory. */
+typedef struct {
+    uint32_t count;             /* rig vertices; equals the attached rig's count */
+    uint32_t weight_count;      /* length of the weight table */
+    const uint32_t* offsets;    /* count + 1 values, non-decreasing, offsets[0] = 0 */
+    const uint32_t* weight_ids; /* offsets[count] entries, each < weight_count */
+    const float* deltas;        /* 3 floats per entry */
+} rsd_morph_desc;
+/* Attach (or replace) the morph table of a scene that has a rig; RSD_ERR_INVALID_ARG without one and on a table
+ * that breaks a rule above (checked on the host, nothing is issued, the scene keeps what it had).  Synchronous
+ * like rsd_scene_attach_rig: it waits for the device, copies the table and allocates the scene's weight table,
+ * zero-filled (rsd_scene_info.device_bytes counts them).  A descriptor with 0 entries detaches; so does
+ * rsd_scene_attach_rig. */
+rsd_status rsd_scene_attach_morph(rsd_scene* scene, const rsd_morph_desc* morph);
+/* rsd_scene_update_pose with a weight table: weights is float[weight_count] (weight_count = the table's), from
+ * device memory (on_device != 0: both `matrices` and `weights` are device pointers) or from host memory.  The
+ * weights are copied into the scene's weight table, the matrices only from host memory; host memory must stay
+ * alive until the copies have run.  Stream-ordered, no host wait, no allocation: the copies, ONE pose launch
+ * (the morph sum runs in the pose kernel, before the blend) and the two refit launches; the entry grid is marked
+ * stale and the call counts as an update.  rsd_scene_update_pose on a scene with a morph table uses the scene's
+ * weight table as the last rsd_scene_update_pose_morph left it (zeros after attach).  RSD_ERR_INVALID_ARG
+ * without a morph table or when a count is not the scene's. */
+rsd_status rsd_scene_update_pose_morph(rsd_scene* scene, const float* matrices, uint32_t matrix_count,
+                                       const float* weights, uint32_t weight_count, uint32_t on_device,
+                                       rsd_stream stream);
+typedef struct {
+    uint32_t attached;      /* 1: the scene has a morph table */
+    uint32_t count;         /* rig vertices the table covers */
+    uint32_t weight_count;  /* weights of a pose */
+    uint32_t entry_count;   /* (weight id, delta) entries */
+    uint64_t morph_bytes;   /* device bytes of the table and the weights */
+} rsd_scene_morph_info;
+rsd_status rsd_scene_morph_info_get(const rsd_scene* scene, rsd_scene_morph_info* out);
+
 /* --- motion tracking: the previous positions of a dynamic scene (DESIGN.md 4 "Motion vectors of moving
  * geometry") ---
  * Opt-in: a scene that never calls rsd_scene_track_motion allocates, behaves and reports as before.

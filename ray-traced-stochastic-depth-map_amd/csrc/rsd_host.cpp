@@ -457,6 +457,16 @@ rsd_status require_dynamic(const rsd_scene* s, const char* who) {
     }
     return RSD_OK;
 }
+
+// free the morph table of a scene (the caller has waited for the device)
+void drop_morph(rsd_scene* s) {
+    if (!s->d_morph) return;
+    (void)hipFree(s->d_morph);
+    s->device_bytes -= s->morph_bytes;
+    s->d_morph = nullptr;
+    s->morph = rsd::MorphData{};
+    s->morph_bytes = 0;
+}
 }  // namespace
 
 extern "C" rsd_status rsd_scene_update_positions(rsd_scene* s, const float* positions, uint32_t vertex_count,
@@ -551,6 +561,7 @@ extern "C" rsd_status rsd_scene_attach_rig(rsd_scene* s, const rsd_rig_desc* rig
         (void)hipFree(s->d_rig);
         s->device_bytes -= s->rig_bytes;
     }
+    drop_morph(s);  // the table was indexed by the old rig's vertices
     s->d_rig = d;
     s->rig.count = n;
     s->rig.matrix_count = nm;
@@ -608,6 +619,122 @@ extern "C" rsd_status rsd_scene_rig_info_get(const rsd_scene* s, rsd_scene_rig_i
     out->matrix_count = s->rig.matrix_count;
     out->reserved = 0;
     out->rig_bytes = s->rig_bytes;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_scene_attach_morph(rsd_scene* s, const rsd_morph_desc* m) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_attach_morph"); st != RSD_OK) return st;
+    auto refuse = [](const std::string& why) {
+        set_error("rsd_scene_attach_morph: " + why);
+        return RSD_ERR_INVALID_ARG;
+    };
+    if (!s->d_rig) return refuse("the scene has no rig (rsd_scene_attach_rig)");
+    if (!m) return refuse("null morph table");
+    const uint32_t n = m->count, nw = m->weight_count;
+    if (n != s->rig.count)
+        return refuse("count " + std::to_string(n) + " is not the rig's " + std::to_string(s->rig.count));
+    if (!m->offsets) return refuse("null offsets");
+    if (m->offsets[0] != 0) return refuse("offsets[0] is " + std::to_string(m->offsets[0]) + ", not 0");
+    for (uint32_t i = 0; i < n; ++i)
+        if (m->offsets[i + 1] < m->offsets[i])
+            return refuse("offsets decrease at rig vertex " + std::to_string(i) + " (" + std::to_string(m->offsets[i]) +
+                          " -> " + std::to_string(m->offsets[i + 1]) + ")");
+    const uint32_t ne = m->offsets[n];
+    if (ne && (!m->weight_ids || !m->deltas)) return refuse("null argument");
+    for (uint32_t e = 0; e < ne; ++e)
+        if (m->weight_ids[e] >= nw)
+            return refuse("weight id " + std::to_string(m->weight_ids[e]) + " is out of range of weight_count " +
+                          std::to_string(nw));
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    // synchronous: a pose in flight has read the table it is about to lose
+    RSD_HIP(hipDeviceSynchronize());
+    if (!ne) {
+        drop_morph(s);
+        return RSD_OK;
+    }
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t oOff = 0, oEnt = al(4 * ((size_t)n + 1)), oW = oEnt + al(16 * (size_t)ne), total = oW + al(4 * (size_t)nw);
+    std::vector<uint32_t> ent(4 * (size_t)ne);
+    for (uint32_t e = 0; e < ne; ++e) {
+        ent[4 * (size_t)e] = m->weight_ids[e];
+        std::memcpy(&ent[4 * (size_t)e + 1], m->deltas + 3 * (size_t)e, 12);
+    }
+    char* d = nullptr;
+    hipError_t e = hipMalloc(&d, total);
+    if (e == hipSuccess) e = hipMemset(d, 0, total);
+    if (e == hipSuccess) e = hipMemcpy(d + oOff, m->offsets, 4 * ((size_t)n + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + oEnt, ent.data(), 16 * (size_t)ne, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return rsd::hip_fail(e, "rsd_scene_attach_morph");
+    }
+    drop_morph(s);
+    s->d_morph = d;
+    s->morph.count = n;
+    s->morph.weight_count = nw;
+    s->morph.entry_count = ne;
+    s->morph.offsets = reinterpret_cast<uint32_t*>(d + oOff);
+    s->morph.entries = reinterpret_cast<uint4*>(d + oEnt);
+    s->morph.weights = reinterpret_cast<float*>(d + oW);
+    s->morph_bytes = total;
+    s->device_bytes += total;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_scene_update_pose_morph(rsd_scene* s, const float* matrices, uint32_t matrix_count,
+                                                  const float* weights, uint32_t weight_count, uint32_t on_device,
+                                                  rsd_stream stream) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_update_pose_morph"); st != RSD_OK) return st;
+    if (!s->d_morph) {
+        set_error("rsd_scene_update_pose_morph: the scene has no morph table (rsd_scene_attach_morph)");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (weight_count != s->morph.weight_count) {
+        set_error("rsd_scene_update_pose_morph: weight_count " + std::to_string(weight_count) + " is not the table's " +
+                  std::to_string(s->morph.weight_count));
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (matrix_count != s->rig.matrix_count) {
+        set_error("rsd_scene_update_pose_morph: matrix_count " + std::to_string(matrix_count) + " is not the rig's " +
+                  std::to_string(s->rig.matrix_count));
+        return RSD_ERR_INVALID_ARG;
+    }
+    if ((!matrices && matrix_count) || (!weights && weight_count)) {
+        set_error("rsd_scene_update_pose_morph: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (on_device && reinterpret_cast<uintptr_t>(matrices) % 16 != 0) {
+        set_error("rsd_scene_update_pose_morph: device matrices must be 16-byte aligned");
+        return RSD_ERR_INVALID_ARG;
+    }
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    hipStream_t hs = (hipStream_t)stream;
+    // the weights always land in the scene's table: rsd_scene_update_pose reads them there later
+    if (weight_count)
+        RSD_HIP(hipMemcpyAsync(s->morph.weights, weights, 4 * (size_t)weight_count,
+                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, hs));
+    const float* d_matrices = matrices;
+    if (!on_device) {
+        if (matrix_count)
+            RSD_HIP(hipMemcpyAsync(s->rig.matrices, matrices, 48 * (size_t)matrix_count, hipMemcpyHostToDevice, hs));
+        d_matrices = s->rig.matrices;
+    }
+    if (rsd_status st = rsd::pose_enqueue(s, d_matrices, hs); st != RSD_OK) return st;
+    s->entry_stale = s->entry_stale || s->d_entry != nullptr;
+    ++s->updates;
+    return rsd::refit_enqueue(s, hs);
+}
+
+extern "C" rsd_status rsd_scene_morph_info_get(const rsd_scene* s, rsd_scene_morph_info* out) {
+    if (!s || !out) {
+        set_error("rsd_scene_morph_info_get: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    out->attached = s->d_morph ? 1u : 0u;
+    out->count = s->morph.count;
+    out->weight_count = s->morph.weight_count;
+    out->entry_count = s->morph.entry_count;
+    out->morph_bytes = s->morph_bytes;
     return RSD_OK;
 }
 
@@ -781,6 +908,7 @@ extern "C" void rsd_scene_release(rsd_scene* s) {
     (void)hipFree(s->d_dyn);
     (void)hipFree(s->dyn.prev_positions);
     (void)hipFree(s->d_rig);
+    (void)hipFree(s->d_morph);
     delete s;
 }
 

@@ -87,6 +87,15 @@ struct RigData {
     float* rest = nullptr;           // float3[count]: what the matrices act on
     float* matrices = nullptr;       // float[matrix_count][12]: where a pose from host memory is copied
 };
+
+// The morph table of a rig (rsd_scene_attach_morph, csrc/skinning.hip): pointers into rsd_scene.d_morph, one
+// allocation.  Offsets and weight ids were checked on the host at attach.
+struct MorphData {
+    uint32_t count = 0, weight_count = 0, entry_count = 0;
+    uint32_t* offsets = nullptr;  // uint32[count + 1]
+    uint4* entries = nullptr;     // {weight id, delta x, delta y, delta z (float bits)} per entry, 16-byte aligned
+    float* weights = nullptr;     // float[weight_count]: the weights of the last pose (zeros after attach)
+};
 }  // namespace rsd
 
 struct rsd_scene {
@@ -129,6 +138,10 @@ struct rsd_scene {
     void* d_rig = nullptr;
     rsd::RigData rig;
     uint64_t rig_bytes = 0;
+    // morph targets of the rig (rsd_scene_attach_morph): d_morph == null without a table
+    void* d_morph = nullptr;
+    rsd::MorphData morph;
+    uint64_t morph_bytes = 0;
 };
 
 namespace rsd {
@@ -155,7 +168,8 @@ rsd_status refit_scatter_enqueue(rsd_scene* s, const uint32_t* d_ids, const floa
 rsd_status refit_enqueue(rsd_scene* s, hipStream_t st);
 // prev_positions <- positions of a scene that tracks motion, one launch on `st`
 rsd_status motion_snapshot_enqueue(rsd_scene* s, hipStream_t st);
-// skinning.hip: pose the rig's vertices into the scene's position copy from `d_matrices` (float[matrix_count][12])
+// skinning.hip: pose the rig's vertices into the scene's position copy from `d_matrices` (float[matrix_count][12]);
+// with a morph table the same launch first adds the table's deltas by the scene's weight table
 rsd_status pose_enqueue(rsd_scene* s, const float* d_matrices, hipStream_t st);
 
 // The previous camera's terms of the motion-vector projection (post.hip motion_vector_kernel, gbuffer_motion.hip):

@@ -72,6 +72,16 @@ class SceneRigInfo(C.Structure):  # rsd_scene_rig_info
                 ("reserved", C.c_uint32), ("rig_bytes", C.c_uint64)]
 
 
+class MorphDesc(C.Structure):  # rsd_morph_desc
+    _fields_ = [("count", C.c_uint32), ("weight_count", C.c_uint32), ("offsets", C.c_void_p),
+                ("weight_ids", C.c_void_p), ("deltas", C.c_void_p)]
+
+
+class SceneMorphInfo(C.Structure):  # rsd_scene_morph_info
+    _fields_ = [("attached", C.c_uint32), ("count", C.c_uint32), ("weight_count", C.c_uint32),
+                ("entry_count", C.c_uint32), ("morph_bytes", C.c_uint64)]
+
+
 class SceneMotionInfo(C.Structure):  # rsd_scene_motion_info
     _fields_ = [("tracked", C.c_uint32), ("reserved", C.c_uint32), ("snapshots", C.c_uint64),
                 ("motion_bytes", C.c_uint64)]
@@ -294,7 +304,8 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_hbao_noise_table", "rsd_sd_raster", "rsd_scene_upload_dynamic", "rsd_scene_update_positions",
            "rsd_scene_update_subset", "rsd_scene_rebuild_entry_grid", "rsd_scene_dynamic_info_get", "rsd_bvh_refit",
            "rsd_scene_attach_rig", "rsd_scene_update_pose", "rsd_scene_rig_info_get", "rsd_scene_track_motion",
-           "rsd_scene_motion_begin_frame", "rsd_scene_motion_info_get", "rsd_gbuffer_motion"]
+           "rsd_scene_motion_begin_frame", "rsd_scene_motion_info_get", "rsd_gbuffer_motion",
+           "rsd_scene_attach_morph", "rsd_scene_update_pose_morph", "rsd_scene_morph_info_get"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -326,8 +337,10 @@ class Texture(C.Structure):
 _lib = None
 
 
-def lib():
-    """Load librsd.so (in-tree).  Raises if it has not been built."""
+def lib(allow_missing=()):
+    """Load librsd.so (in-tree).  Raises if it has not been built.  allow_missing: names of the morph calls that
+    the library may lack -- only for a tool that loads an older build beside this one (tools/morph_time.py); every
+    other caller gets an AttributeError for a missing export."""
     global _lib
     if _lib is None:
         if not LIB_PATH.exists():
@@ -366,6 +379,13 @@ def lib():
         L.rsd_scene_update_pose.argtypes = [vp, vp, u32, u32, vp]
         L.rsd_scene_rig_info_get.restype = st
         L.rsd_scene_rig_info_get.argtypes = [vp, C.POINTER(SceneRigInfo)]
+        for name, argtypes in (("rsd_scene_attach_morph", [vp, C.POINTER(MorphDesc)]),
+                               ("rsd_scene_update_pose_morph", [vp, vp, u32, vp, u32, u32, vp]),
+                               ("rsd_scene_morph_info_get", [vp, C.POINTER(SceneMorphInfo)])):
+            if name in allow_missing and not hasattr(L, name):
+                continue
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = st, argtypes
         L.rsd_scene_track_motion.restype = st
         L.rsd_scene_track_motion.argtypes = [vp]
         L.rsd_scene_motion_begin_frame.restype = st

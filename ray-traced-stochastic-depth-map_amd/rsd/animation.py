@@ -193,10 +193,14 @@ class AnimationController:
     """The scene graph and its animations: `nodes` is a list of (local matrix 4x4, parent id or INVALID_ID), parents
     before children; `matrix_nodes` names the nodes whose global matrices a pose consists of, in matrix order."""
 
-    def __init__(self, nodes, animations, matrix_nodes=()):
+    def __init__(self, nodes, animations, matrix_nodes=(), matrix_binds=None):
+        """`animations`: anything with `.nodeID` and `.animate(t)` -> local 4x4 (Animation, rsd.gltf.NodeAnimation).
+        matrix_binds: per matrix a float64 4x4 the node's global matrix is multiplied with on the right -- a skin's
+        inverse bind matrix -- or None for the global matrix itself; None: no matrix has one."""
         self.nodes = [(np.asarray(m, np.float64).reshape(4, 4), int(p)) for m, p in nodes]
         self.animations = list(animations)
         self.matrix_nodes = [int(n) for n in matrix_nodes]
+        self.matrix_binds = None if matrix_binds is None else list(matrix_binds)
         for i, (_, p) in enumerate(self.nodes):
             if p != INVALID_ID and not 0 <= p < i:
                 raise ValueError(f"node {i}: parent {p} must come before it")
@@ -228,9 +232,63 @@ class AnimationController:
         """The pose at time t: float32 [len(matrix_nodes), 12], each element rounded once."""
         g = self.global_matrices(t)
         out = np.zeros((len(self.matrix_nodes), 12), np.float32)
+        binds = self.matrix_binds
         for k, n in enumerate(self.matrix_nodes):
-            out[k] = g[n][:3, :].astype(np.float32).reshape(12)
+            m = g[n] if binds is None or binds[k] is None else g[n] @ binds[k]
+            out[k] = m[:3, :].astype(np.float32).reshape(12)
         return out
+
+
+class MorphTable:
+    """rsd_morph_desc on the host: per rig vertex a run of (weight id, delta) entries in CSR form -- `offsets`
+    [count + 1], `weight_ids` [entries], `deltas` [entries, 3] -- into a table of `weight_count` weights.
+    `sources`: where the weights of time t come from, a list of (first weight id, default weights float64 [k],
+    channel or None); a channel is anything with `.weights(t)` -> k values (rsd.gltf.WeightAnimation)."""
+
+    def __init__(self, offsets, weight_ids, deltas, weight_count, sources=()):
+        self.offsets = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+        n = int(self.offsets[-1]) if self.offsets.size else 0
+        self.weight_ids = np.ascontiguousarray(weight_ids, np.uint32).reshape(n)
+        self.deltas = np.ascontiguousarray(deltas, np.float32).reshape(n, 3)
+        self.weight_count = int(weight_count)
+        self.sources = list(sources)
+
+    @property
+    def count(self) -> int:
+        return max(int(self.offsets.size) - 1, 0)
+
+    @property
+    def entry_count(self) -> int:
+        return int(self.weight_ids.size)
+
+    @staticmethod
+    def from_targets(blocks, sources=()) -> "MorphTable":
+        """blocks: per run of rig vertices (n, first weight id, targets) with targets a list of float32 [n, 3] deltas
+        or None for vertices without targets.  Target k of a vertex becomes an entry only if a component of its
+        delta is not +-0; a vertex's entries are in target order."""
+        counts, ids, deltas, nw = [], [], [], 0
+        for n, base, targets in blocks:
+            if not targets:
+                counts.append(np.zeros(n, np.int64))
+                continue
+            d = np.stack([np.asarray(t, np.float32).reshape(n, 3) for t in targets], 1)  # [n, k, 3]
+            live = (d != 0.0).any(axis=2)  # -0.0 != 0.0 is false: +-0 deltas drop out
+            v, k = np.nonzero(live)        # row-major: by vertex, then by target
+            counts.append(live.sum(axis=1))
+            ids.append((base + k).astype(np.uint32))
+            deltas.append(d[v, k])
+            nw = max(nw, base + d.shape[1])
+        nw = max([nw] + [b + len(w) for b, w, _ in sources])
+        off = np.concatenate([[0], np.cumsum(np.concatenate(counts) if counts else np.zeros(0, np.int64))])
+        return MorphTable(off, np.concatenate(ids) if ids else np.zeros(0, np.uint32),
+                          np.concatenate(deltas) if deltas else np.zeros((0, 3), np.float32), nw, sources)
+
+    def weights(self, t) -> np.ndarray:
+        """The weight table at time t, float32 [weight_count]: evaluated in float64 and rounded once."""
+        w = np.zeros(self.weight_count, np.float64)
+        for base, default, channel in self.sources:
+            w[base:base + len(default)] = default if channel is None else channel.weights(t)
+        return w.astype(np.float32)
 
 
 class Rig:
@@ -238,9 +296,10 @@ class Rig:
     and `weights` [count, 4] their influences into a table of `matrix_count` matrices.  `rest` [count, 3]: the
     positions the matrices act on (None: the scene's positions when the rig is attached).  `controller`: an
     AnimationController whose matrices(t) is this rig's pose at time t (None for a rig posed by the caller).
-    A rigid vertex of matrix m is ids (m, 0, 0, 0), weights (1, 0, 0, 0)."""
+    A rigid vertex of matrix m is ids (m, 0, 0, 0), weights (1, 0, 0, 0).  `morph`: a MorphTable over the rig's
+    vertices (rsd_morph_desc), or None."""
 
-    def __init__(self, vertex_ids, matrix_ids, weights, matrix_count, rest=None, controller=None):
+    def __init__(self, vertex_ids, matrix_ids, weights, matrix_count, rest=None, controller=None, morph=None):
         self.vertex_ids = np.ascontiguousarray(vertex_ids, np.uint32).reshape(-1)
         n = self.vertex_ids.size
         self.matrix_ids = np.ascontiguousarray(matrix_ids, np.uint32).reshape(n, 4)
@@ -248,6 +307,15 @@ class Rig:
         self.matrix_count = int(matrix_count)
         self.rest = None if rest is None else np.ascontiguousarray(rest, np.float32).reshape(n, 3)
         self.controller = controller
+        if morph is not None and morph.count != n:
+            raise ValueError(f"Rig: the morph table covers {morph.count} vertices, the rig has {n}")
+        self.morph = morph
+
+    def morph_weights(self, t) -> np.ndarray:
+        """The morph weights at time t, float32 [morph.weight_count]."""
+        if self.morph is None:
+            raise ValueError("this rig has no morph table")
+        return self.morph.weights(t)
 
     @property
     def count(self) -> int:
@@ -267,6 +335,22 @@ class Rig:
         if self.controller is None:
             raise ValueError("this rig has no animation controller: pose it with update_pose(matrices)")
         return self.controller.matrices(t)
+
+
+def morph_positions(rest, morph: MorphTable, weights) -> np.ndarray:
+    """rsd_scene_update_pose_morph's morph sum on the host in float32: per rig vertex, for its entries in ascending
+    order, p = p + (w[id] * delta), the product rounded, then the sum.  What pose_positions is then given in place
+    of the rest positions."""
+    F = np.float32
+    p = np.array(rest, F).reshape(-1, 3)
+    w = np.asarray(weights, F).reshape(-1)
+    off = morph.offsets.astype(np.int64)
+    n = off[1:] - off[:-1]
+    for k in range(int(n.max()) if n.size else 0):
+        v = np.flatnonzero(n > k)
+        e = off[v] + k
+        p[v] = p[v] + (w[morph.weight_ids[e]][:, None] * morph.deltas[e]).astype(F)
+    return p
 
 
 def pose_positions(rest, matrix_ids, weights, matrices) -> np.ndarray:

@@ -212,6 +212,13 @@ def host_bvh_refit(bvh, tri_offset: int, indices, positions):
     return out
 
 
+def rig_has_morph(rig) -> bool:
+    """A rig whose morph table has entries: one without (every delta +-0) is posed like a rig without a table, since
+    rsd_scene_attach_morph detaches on a table of 0 entries."""
+    morph = getattr(rig, "morph", None)
+    return morph is not None and morph.entry_count > 0
+
+
 class GpuScene:
     def __init__(self, dev: Device, scene: Scene, dynamic: bool = False, motion: bool = False):
         """dynamic=True: rsd_scene_upload_dynamic -- the scene's vertices can move (update_positions,
@@ -304,6 +311,39 @@ class GpuScene:
                         rig.weights.ctypes.data, rig.rest.ctypes.data if rig.rest is not None else None)
         abi.check(abi.lib().rsd_scene_attach_rig(self.h, C.byref(d)), "rsd_scene_attach_rig")
         self.rig = rig
+        if rig_has_morph(rig):
+            self.attach_morph(rig.morph)
+
+    def attach_morph(self, morph):
+        """rsd_scene_attach_morph: `morph` (rsd.animation.MorphTable) over the attached rig's vertices.  Synchronous;
+        replaces an earlier table, a table without entries detaches; attach_rig drops it."""
+        d = abi.MorphDesc(morph.count, morph.weight_count, morph.offsets.ctypes.data, morph.weight_ids.ctypes.data,
+                          morph.deltas.ctypes.data)
+        abi.check(abi.lib().rsd_scene_attach_morph(self.h, C.byref(d)), "rsd_scene_attach_morph")
+
+    def update_pose_morph(self, matrices, weights, stream=None):
+        """Pose the rig's vertices from morph weights and matrices and refit (rsd_scene_update_pose_morph): `matrices`
+        as for update_pose, `weights` float32 [weight_count]; both numpy arrays (copied from the host on the stream,
+        kept alive here until the next update) or both contiguous float32 torch tensors on the scene's device."""
+        on_device = [not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") for a in (matrices, weights)]
+        if on_device[0] != on_device[1]:
+            raise ValueError("update_pose_morph: matrices and weights must both be on the host or both on the GPU")
+        if on_device[0]:
+            m, w = matrices.contiguous(), weights.contiguous()
+            if not (m.is_cuda and w.is_cuda) or {str(m.dtype), str(w.dtype)} != {"torch.float32"}:
+                raise ValueError("update_pose_morph: tensors must be float32 and on the GPU")
+            args = (m.data_ptr(), m.numel() // 12, w.data_ptr(), w.numel(), 1)
+        else:
+            m, w = np.ascontiguousarray(matrices, np.float32), np.ascontiguousarray(weights, np.float32)
+            args = (m.ctypes.data, m.size // 12, w.ctypes.data, w.size, 0)
+        abi.check(abi.lib().rsd_scene_update_pose_morph(self.h, *args, self._stream(stream)),
+                  "rsd_scene_update_pose_morph")
+        self._keep = (m, w)
+
+    def morph_info(self) -> abi.SceneMorphInfo:
+        d = abi.SceneMorphInfo()
+        abi.check(abi.lib().rsd_scene_morph_info_get(self.h, C.byref(d)), "rsd_scene_morph_info_get")
+        return d
 
     def update_pose(self, matrices, stream=None):
         """Pose the rig's vertices and refit (rsd_scene_update_pose): `matrices` is float32 [matrix_count, 12] -- the
@@ -323,10 +363,14 @@ class GpuScene:
 
     def animate(self, t, stream=None):
         """The scene at animation time t: the rig's controller is evaluated on the host (rsd.animation) and its
-        matrices go to update_pose."""
+        matrices go to update_pose -- with the morph weights of time t (update_pose_morph) when the rig has a morph
+        table."""
         if self.rig is None:
             raise ValueError("animate: the scene has no rig")
-        self.update_pose(self.rig.matrices(t), stream)
+        if rig_has_morph(self.rig):
+            self.update_pose_morph(self.rig.matrices(t), self.rig.morph_weights(t), stream)
+        else:
+            self.update_pose(self.rig.matrices(t), stream)
 
     def rig_info(self) -> abi.SceneRigInfo:
         d = abi.SceneRigInfo()

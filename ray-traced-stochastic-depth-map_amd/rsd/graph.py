@@ -102,6 +102,7 @@ class RenderGraph:
         motion (GpuScene(dynamic=True, motion=True)), GBufferRaster.mvec follows the moving geometry and the pass
         snapshots the positions after each execute; nothing else is needed here."""
         abi.check(self._L.rsd_graph_set_scene(self._h, scene_handle, C.byref(camera)), "set_scene")
+        self._scene_h = scene_handle
         if rig is not None:
             self._rig = rig
 
@@ -136,11 +137,21 @@ class RenderGraph:
 
     def animate(self, t, stream=None):
         """The scene at animation time t: the rig given to set_scene evaluates its controller on the host and the
-        pose goes to update_pose; the next execute on that stream renders it."""
+        pose goes to update_pose; the next execute on that stream renders it.  A rig with a morph table is posed with
+        its weights of time t by rsd_scene_update_pose_morph on the scene itself (the graph's update calls only pass
+        the scene's on: passes read its device tree every execute)."""
+        import numpy as np
         rig = getattr(self, "_rig", None)
         if rig is None:
             raise ValueError("animate: set_scene was given no rig")
-        self.update_pose(rig.matrices(t), stream)
+        from .frame import rig_has_morph
+        if not rig_has_morph(rig):
+            self.update_pose(rig.matrices(t), stream)
+            return
+        m, w = np.ascontiguousarray(rig.matrices(t), np.float32), np.ascontiguousarray(rig.morph_weights(t), np.float32)
+        abi.check(abi.lib().rsd_scene_update_pose_morph(self._scene_h, m.ctypes.data, m.size // 12, w.ctypes.data,
+                                                        w.size, 0, stream), "rsd_scene_update_pose_morph")
+        self._keep = [m, w]
 
     def set_input(self, name: str, ptr: int, width: int, height: int, fmt: int, layers: int = 1):
         t = abi.Texture(C.c_void_p(ptr), width, height, layers, fmt, 0)

@@ -15,7 +15,8 @@ indices, `d`/`Tr` constant alpha, `map_d` / the alpha channel of `map_Kd` as the
 texture) and `read_image` (PNG via zlib, binary/ASCII PGM/PPM/PAM, .npy) for alpha textures.
 A material with an alpha texture or a constant alpha below 1 is AlphaMode::Mask (Falcor's
 importers mark such materials Mask; the threshold defaults to 0.5, MaterialData.slang:99).
-Binary FBX 7.x: rsd.fbx.load_fbx (the same SceneBuilder).  glTF, USD and PBRT are out of scope."""
+Binary FBX 7.x: rsd.fbx.load_fbx; glTF 2.0 with skins, animations and morph targets: rsd.gltf.load_gltf (the same
+SceneBuilder).  USD and PBRT are out of scope."""
 from __future__ import annotations
 
 import dataclasses
@@ -47,6 +48,12 @@ class Mesh:
     texcoords: np.ndarray | None = None  # float32 [nv, 2]
     material: int = 0
     front_face_cw: bool = False         # TriangleMesh::getFrontFaceCW
+    # linear-blend skinning and morph targets (rsd.gltf): four joints of the instance's skin per vertex and their
+    # weights, used as stored; position deltas per morph target and the targets' default weights
+    joints: np.ndarray | None = None         # uint32 [nv, 4]
+    weights: np.ndarray | None = None        # float32 [nv, 4]
+    morph_targets: list | None = None        # float32 [nv, 3] per target
+    morph_weights: np.ndarray | None = None  # float64 [targets]
 
 
 class SceneBuilder:
@@ -61,6 +68,12 @@ class SceneBuilder:
         self.nodes: list[tuple[np.ndarray, int]] = []
         self.animations: list[anim.Animation] = []
         self.instance_nodes: list[int | None] = []
+        # skins: (joint nodes, inverse bind matrices float64 [joints, 4, 4]); the skin and the morph weights of an
+        # instance, by instance index; weight channels: anything with .nodeID and .weights(t)
+        self.skins: list[tuple[list, np.ndarray]] = []
+        self.instance_skins: dict[int, int] = {}
+        self.instance_morph_weights: dict[int, np.ndarray] = {}
+        self.weight_animations: list = []
         self.camera = {"pos": [0.0, 0.0, 5.0], "target": [0.0, 0.0, 0.0], "up": [0.0, 1.0, 0.0]}
 
     def add_material(self, m: Material) -> int:
@@ -79,16 +92,39 @@ class SceneBuilder:
         self.meshes.append(mesh)
         return len(self.meshes) - 1
 
-    def add_node(self, matrix=None, parent: int = anim.INVALID_ID) -> int:
-        m = np.eye(4, dtype=np.float32) if matrix is None else np.asarray(matrix, np.float32).reshape(4, 4)
+    def add_node(self, matrix=None, parent: int = anim.INVALID_ID, dtype=np.float32) -> int:
+        """dtype: the precision the local matrix is kept in (float64: an importer that composes in double)."""
+        m = np.eye(4, dtype=dtype) if matrix is None else np.asarray(matrix, dtype).reshape(4, 4)
         if parent != anim.INVALID_ID and not 0 <= parent < len(self.nodes):
             raise ValueError(f"add_node: parent {parent} does not exist")
         self.nodes.append((m, parent))
         return len(self.nodes) - 1
 
-    def add_instance(self, mesh_id: int, transform=None, node: int | None = None):
+    def add_skin(self, joint_nodes, inverse_bind=None) -> int:
+        """joint_nodes: the node of each joint; inverse_bind: float [joints, 4, 4], default identities."""
+        joints = [int(j) for j in joint_nodes]
+        if any(not 0 <= j < len(self.nodes) for j in joints):
+            raise ValueError("add_skin: a joint names a node that does not exist")
+        ibm = (np.tile(np.eye(4), (len(joints), 1, 1)) if inverse_bind is None
+               else np.asarray(inverse_bind, np.float64).reshape(len(joints), 4, 4))
+        self.skins.append((joints, ibm))
+        return len(self.skins) - 1
+
+    def add_instance(self, mesh_id: int, transform=None, node: int | None = None, skin: int | None = None,
+                     morph_weights=None):
         """node: the scene-graph node the instance hangs on (its world matrix at rest is `transform`); it matters
-        only when that node or one above it is animated."""
+        only when that node or one above it is animated, or when the mesh has morph targets.  skin: the skin that
+        poses the mesh's joints (the mesh then needs `joints` and `weights`; `transform` and the node's own
+        matrix do not act on it).  morph_weights: this instance's default morph weights, over the mesh's."""
+        if skin is not None:
+            m = self.meshes[mesh_id]
+            if not 0 <= skin < len(self.skins) or m.joints is None or m.weights is None:
+                raise ValueError("add_instance: a skinned instance needs a skin and a mesh with joints and weights")
+            if int(np.asarray(m.joints).max(initial=0)) >= len(self.skins[skin][0]):
+                raise ValueError("add_instance: a joint index is out of range of the skin")
+            self.instance_skins[len(self.instances)] = skin
+        if morph_weights is not None:
+            self.instance_morph_weights[len(self.instances)] = np.asarray(morph_weights, np.float64).reshape(-1)
         t = np.eye(4, dtype=np.float32) if transform is None else np.asarray(transform, np.float32).reshape(4, 4)
         if node is not None and not 0 <= node < len(self.nodes):
             raise ValueError(f"add_instance: node {node} does not exist")
@@ -112,30 +148,71 @@ class SceneBuilder:
         pos, ind, flg, uv, mat = [], [], [], [], []
         nv = 0
         controller, moving, rest_pose, matrix_of = None, set(), None, {}
-        rig_ids, rig_mats, rig_rest = [], [], []
-        if animated and self.animations:
+        rig_ids, rig_mats, rig_rest, rig_w, morph_blocks, morph_sources = [], [], [], [], [], []
+        nodes_of = self.instance_nodes + [None] * (len(self.instances) - len(self.instance_nodes))
+        morphed = {k for k, (mesh_id, _) in enumerate(self.instances)
+                   if self.meshes[mesh_id].morph_targets and (nodes_of[k] is not None or k in self.instance_skins)}
+        if animated and (self.animations or self.instance_skins or morphed):
             controller = anim.AnimationController(self.nodes, self.animations)
-            moving = controller.animated_nodes()
-            nodes_of = self.instance_nodes + [None] * (len(self.instances) - len(self.instance_nodes))
-            for n in nodes_of:
-                if n in moving and n not in matrix_of:
+            # a morphed instance is posed like an animated one, rigid on its node's matrix
+            moving = controller.animated_nodes() | {nodes_of[k] for k in morphed if k not in self.instance_skins}
+            binds = []
+            for k, n in enumerate(nodes_of):
+                if k in self.instance_skins:
+                    sk = self.instance_skins[k]
+                    for j, (jn, ibm) in enumerate(zip(*self.skins[sk])):  # one matrix per (skin, joint): G * IBM
+                        if ("skin", sk, j) not in matrix_of:
+                            matrix_of["skin", sk, j] = len(matrix_of)
+                            controller.matrix_nodes.append(jn)
+                            binds.append(ibm)
+                elif n in moving and n not in matrix_of:
                     matrix_of[n] = len(matrix_of)
-            controller.matrix_nodes = list(matrix_of)
+                    controller.matrix_nodes.append(n)
+                    binds.append(None)
+            if self.instance_skins:
+                controller.matrix_binds = binds
             rest_pose = controller.matrices(0.0)
+        weight_count = 0
         for k, (mesh_id, T) in enumerate(self.instances):
             m = self.meshes[mesh_id]
             mt = self.materials[m.material]
             node = self.instance_nodes[k] if controller is not None and k < len(self.instance_nodes) else None
-            if node is not None and node in moving:
-                slot = matrix_of[node]
-                T = np.eye(4, dtype=np.float32)
-                T[:3, :] = rest_pose[slot].reshape(3, 4)
-                one = np.zeros((len(m.positions), 4), np.float32)
-                one[:, 0] = 1.0
-                p = anim.pose_positions(m.positions, np.full((len(m.positions), 4), [slot, 0, 0, 0], np.uint32), one,
-                                        rest_pose)
-                rig_ids.append(np.arange(nv, nv + len(p), dtype=np.uint32))
-                rig_mats.append(np.full(len(p), slot, np.uint32))
+            skin = self.instance_skins.get(k) if controller is not None else None
+            if skin is not None or (node is not None and node in moving):
+                n = len(m.positions)
+                if skin is not None:
+                    first = matrix_of["skin", skin, 0] if self.skins[skin][0] else 0
+                    ids = (np.asarray(m.joints, np.uint32).reshape(n, 4) + np.uint32(first)).astype(np.uint32)
+                    w = np.asarray(m.weights, np.float32).reshape(n, 4)
+                    T = np.eye(4, dtype=np.float32)  # the node's own transform does not act on a skinned mesh
+                else:
+                    slot = matrix_of[node]
+                    T = np.eye(4, dtype=np.float32)
+                    T[:3, :] = rest_pose[slot].reshape(3, 4)
+                    ids = np.full((n, 4), [slot, 0, 0, 0], np.uint32)
+                    w = np.zeros((n, 4), np.float32)
+                    w[:, 0] = 1.0
+                start = m.positions
+                if k in morphed:
+                    default = np.zeros(len(m.morph_targets), np.float64)
+                    for src in (m.morph_weights, self.instance_morph_weights.get(k)):
+                        if src is not None:
+                            default[:len(src)] = np.asarray(src, np.float64)[:len(default)]
+                    channel = None
+                    for a in self.weight_animations:  # a later channel of a node wins, like the node animations
+                        if a.nodeID == node:
+                            channel = a
+                    morph_blocks.append((n, weight_count, m.morph_targets))
+                    morph_sources.append((weight_count, default, channel))
+                    one = anim.MorphTable.from_targets([(n, 0, m.morph_targets)], [(0, default, channel)])
+                    start = anim.morph_positions(m.positions, one, one.weights(0.0))
+                    weight_count += len(default)
+                else:
+                    morph_blocks.append((n, 0, None))
+                p = anim.pose_positions(start, ids, w, rest_pose)
+                rig_ids.append(np.arange(nv, nv + n, dtype=np.uint32))
+                rig_mats.append(ids)
+                rig_w.append(w)
                 rig_rest.append(m.positions)
             else:
                 # object -> world in float32 (transformPoint)
@@ -171,8 +248,9 @@ class SceneBuilder:
         rig = None
         if controller is not None:
             cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dt)  # noqa: E731
-            rig = anim.Rig.rigid(cat(rig_ids, 0, np.uint32), cat(rig_mats, 0, np.uint32), len(matrix_of),
-                                 rest=cat(rig_rest, (0, 3), np.float32), controller=controller)
+            morph = anim.MorphTable.from_targets(morph_blocks, morph_sources) if morph_sources else None
+            rig = anim.Rig(cat(rig_ids, 0, np.uint32), cat(rig_mats, (0, 4), np.uint32), cat(rig_w, (0, 4), np.float32),
+                           len(matrix_of), rest=cat(rig_rest, (0, 3), np.float32), controller=controller, morph=morph)
         return Scene(name, positions, indices, flags, self.camera, alpha, rig)
 
 

@@ -34,7 +34,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import fbx, ingest
+from . import fbx, gltf, ingest
 from .animation import Animation
 
 F32 = np.float32
@@ -306,13 +306,14 @@ class TriangleMesh:
 
     @staticmethod
     def createFromFile(path, smoothNormals=False):
-        """:195-273 (Assimp, pre-transformed, UVs flipped): OBJ (rsd.ingest) and binary FBX (rsd.fbx) files."""
+        """:195-273 (Assimp, pre-transformed, UVs flipped): OBJ (rsd.ingest), binary FBX (rsd.fbx) and glTF 2.0
+        (rsd.gltf) files."""
         p = _resolve(path)
         if p is None:
             return None  # the reference logs a warning and returns nullptr
-        if p.suffix.lower() not in (".obj", ".fbx"):
-            raise NotImplementedError(f"TriangleMesh.createFromFile: {p.suffix} needs Assimp (OBJ / FBX here)")
-        b = ingest.load_obj(p) if p.suffix.lower() == ".obj" else fbx.load_fbx(p)
+        if p.suffix.lower() not in _IMPORTERS:
+            raise NotImplementedError(f"TriangleMesh.createFromFile: {p.suffix} needs Assimp (OBJ / FBX / glTF here)")
+        b = _IMPORTERS[p.suffix.lower()](p)
         m = TriangleMesh()
         for mesh_id, T in b.instances:
             mm = b.meshes[mesh_id]
@@ -495,6 +496,11 @@ class Camera:
 _SCRIPT_DIR: list[Path] = []
 
 
+# mesh-file importers by extension: each takes (path, builder=None) and returns the rsd.ingest.SceneBuilder
+_IMPORTERS = {".obj": ingest.load_obj, ".fbx": fbx.load_fbx, ".gltf": gltf.load_gltf_builder,
+              ".glb": gltf.load_gltf_builder}
+
+
 def _resolve(path) -> Path | None:
     """Falcor's data-directory search, reduced to: absolute, or relative to the script."""
     p = Path(str(path).replace("\\", "/"))
@@ -546,16 +552,16 @@ class PySceneBuilder:
 
     # -- geometry
     def importScene(self, path, dict=None):
-        """SceneBuilder::import: OBJ through rsd.ingest.load_obj, binary FBX through rsd.fbx.load_fbx (the
-        reference's AssimpImporter); their meshes are placed by the importer itself (world space, like
-        Assimp's node transforms)."""
+        """SceneBuilder::import: OBJ through rsd.ingest.load_obj, binary FBX through rsd.fbx.load_fbx, glTF 2.0
+        (.gltf / .glb) through rsd.gltf.load_gltf_builder (the reference's AssimpImporter); their meshes are placed
+        by the importer itself (world space, like Assimp's node transforms)."""
         p = _resolve(path)
         if p is None:
             raise FileNotFoundError(f"importScene: can't find '{path}'")
-        if p.suffix.lower() not in (".obj", ".fbx"):
-            raise NotImplementedError(f"importScene: no importer for '{p.suffix}' in this build (OBJ, FBX)")
+        if p.suffix.lower() not in _IMPORTERS:
+            raise NotImplementedError(f"importScene: no importer for '{p.suffix}' in this build (OBJ, FBX, glTF)")
         before = len(self._B.materials)
-        (ingest.load_obj if p.suffix.lower() == ".obj" else fbx.load_fbx)(p, builder=self._B)
+        _IMPORTERS[p.suffix.lower()](p, builder=self._B)
         for idx in range(before, len(self._B.materials)):
             w = StandardMaterial(_wrap=self._B.materials[idx])
             self._mat_ids[id(w)] = idx
@@ -679,7 +685,7 @@ def load_pyscene(path, builder: ingest.SceneBuilder | None = None) -> ingest.Sce
 
 
 def load_scene_file(path, **kw) -> ingest.SceneBuilder:
-    """.pyscene, .obj or .fbx by extension."""
+    """.pyscene, .obj, .fbx, .gltf or .glb by extension."""
     p = Path(path)
     if p.suffix.lower() == ".pyscene":
         return load_pyscene(p, **kw)
@@ -687,4 +693,6 @@ def load_scene_file(path, **kw) -> ingest.SceneBuilder:
         return ingest.load_obj(p, **kw)
     if p.suffix.lower() == ".fbx":
         return fbx.load_fbx(p, **kw)
-    raise NotImplementedError(f"{p.suffix}: no importer in this build (.pyscene, .obj, .fbx)")
+    if p.suffix.lower() in (".gltf", ".glb"):
+        return gltf.load_gltf_builder(p, **kw)
+    raise NotImplementedError(f"{p.suffix}: no importer in this build (.pyscene, .obj, .fbx, .gltf, .glb)")
