@@ -334,6 +334,29 @@ rsd_status rsd_scene_dynamic_info_get(const rsd_scene* scene, rsd_scene_dynamic_
  * an update leaves on the device.  RSD_ERR_UNSUPPORTED for a tree with spatial splits. */
 rsd_status rsd_bvh_refit(const void* bvh, uint64_t bvh_bytes, uint32_t tri_offset, const uint32_t* indices,
                          uint32_t triangle_count, const float* positions, uint32_t vertex_count, void* dst);
+/* Rebuild the topology of a dynamic scene on the GPU, in place (DESIGN.md 4 "Rebuilding topology on the GPU"):
+ * the tree the host builder chose for the upload's positions is thrown away and a 4-wide LBVH (Morton codes of
+ * the current positions, Karras's radix tree collapsed two binary levels per node) takes its place in the same
+ * rsd_scene; the bytes are rsd_bvh_build_lbvh's of the current positions.  Synchronous: waits for the device,
+ * builds into new allocations, reads the node count and the depth back, swaps the tree in and frees the old one
+ * and the scratch.  Replaced: the nodes and records, the refit's per-node tables, the primitive -> record map,
+ * rsd_scene_info's node_count / max_depth / wide_depth / leaf_count (sah_cost becomes 0: it is not computed).
+ * The entry grid is marked stale (rsd_scene_rebuild_entry_grid builds it from the new tree).  Untouched: the
+ * positions, the rig, the morph table, alpha data, motion tracking and rsd_scene_dynamic_info.updates.
+ * RSD_ERR_INVALID_ARG on a scene that is not dynamic. */
+rsd_status rsd_scene_rebuild_bvh(rsd_scene* scene);
+typedef struct {
+    uint64_t rebuilds;    /* rsd_scene_rebuild_bvh calls that succeeded */
+    uint32_t node_count;  /* wide nodes of the scene's tree now */
+    uint32_t wide_depth;  /* wide nodes on its longest path (the root counts 1) */
+    double device_ms;     /* the last rebuild on the device: first launch to last, the read-back between them
+                             included; 0 before the first */
+} rsd_scene_rebuild_info;
+rsd_status rsd_scene_rebuild_info_get(const rsd_scene* scene, rsd_scene_rebuild_info* out);
+/* The same tree without a GPU: rsd_bvh_build's contract and byte layout, the LBVH of desc's positions instead of
+ * the SAH tree (deterministic; single-threaded).  RSD_ERR_UNSUPPORTED for 2^30 triangles and more. */
+rsd_status rsd_bvh_build_lbvh(const rsd_scene_desc* desc, void* dst, uint64_t capacity, uint64_t* bytes,
+                              uint32_t* tri_offset);
 
 /* --- animated scenes: a rig and a pose kernel (DESIGN.md 4 "Animated scenes") -------------------
  * A rig names `count` vertices of a dynamic scene and gives each four (matrix id, weight) influences into a

@@ -15,6 +15,7 @@
 
 #include "bvh_refit.h"
 #include "entry_grid.h"
+#include "lbvh.h"
 #include "rsd_internal.h"
 
 namespace rsd {
@@ -139,10 +140,9 @@ rsd_status upload_dynamic_data(rsd_scene* s, const rsd_scene_desc* desc, const r
         set_error("rsd_scene_upload_dynamic: the built tree is not one a refit can walk");
         return RSD_ERR_UNSUPPORTED;
     }
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t oInd = 0, oPos = al(12 * (size_t)nt), oPar = oPos + al(12 * (size_t)nv), oInner = oPar + al(4 * (size_t)nn),
-                 oArr = oInner + al(4 * (size_t)nn), oTight = oArr + al(4 * (size_t)nn),
-                 total = oTight + al(24 * (size_t)nn);
+    const rsd::DynLayout lay = rsd::dyn_layout(nt, nv, nn);
+    const size_t oInd = lay.indices, oPos = lay.positions, oPar = lay.parent, oInner = lay.inner, oArr = lay.arrive,
+                 oTight = lay.tight, total = lay.total;
     char* d = nullptr;
     hipError_t e = hipMalloc(&d, total);
     if (e == hipSuccess) e = hipMemset(d, 0, total);
@@ -801,6 +801,59 @@ extern "C" rsd_status rsd_scene_rebuild_entry_grid(rsd_scene* s) {
                                       "rsd_scene_rebuild_entry_grid");
     if (st != RSD_OK) return st;
     s->entry_stale = false;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_scene_rebuild_bvh(rsd_scene* s) {
+    if (rsd_status st = require_dynamic(s, "rsd_scene_rebuild_bvh"); st != RSD_OK) return st;
+    if (s->triangle_count > rsd::kLbvhMaxTriangles ||
+        rsd::lbvh_depth_bound(s->triangle_count) > rsd::kLbvhMaxWideDepth) {
+        set_error("rsd_scene_rebuild_bvh: too many triangles for the walks' stacks");
+        return RSD_ERR_UNSUPPORTED;
+    }
+    RSD_HIP(hipSetDevice(s->dev->hip_device));
+    return rsd::lbvh_rebuild(s);
+}
+
+extern "C" rsd_status rsd_scene_rebuild_info_get(const rsd_scene* s, rsd_scene_rebuild_info* out) {
+    if (!s || !out) {
+        set_error("rsd_scene_rebuild_info_get: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    out->rebuilds = s->rebuilds;
+    out->node_count = s->node_count;
+    out->wide_depth = s->stats.wide_depth;
+    out->device_ms = s->rebuild_ms;
+    return RSD_OK;
+}
+
+extern "C" rsd_status rsd_bvh_build_lbvh(const rsd_scene_desc* desc, void* dst, uint64_t capacity, uint64_t* bytes,
+                                         uint32_t* tri_offset) {
+    if (!desc || !bytes || (desc->triangle_count && (!desc->positions || !desc->indices))) {
+        set_error("rsd_bvh_build_lbvh: null argument");
+        return RSD_ERR_INVALID_ARG;
+    }
+    if (desc->triangle_count > rsd::kLbvhMaxTriangles ||
+        rsd::lbvh_depth_bound(desc->triangle_count) > rsd::kLbvhMaxWideDepth) {
+        set_error("rsd_bvh_build_lbvh: too many triangles for the walks' stacks");
+        return RSD_ERR_UNSUPPORTED;
+    }
+    for (uint64_t i = 0; i < 3ull * desc->triangle_count; ++i)
+        if (desc->indices[i] >= desc->vertex_count) {
+            set_error("rsd_bvh_build_lbvh: index out of range of vertex_count");
+            return RSD_ERR_INVALID_ARG;
+        }
+    std::vector<uint32_t> words;
+    const rsd::LbvhResult res = rsd::lbvh_build_host(desc->positions, desc->vertex_count, desc->indices,
+                                                     desc->triangle_count, desc->triangle_flags, words);
+    *bytes = words.size() * 4;  // the layout of rsd_scene_upload's allocation
+    if (tri_offset) *tri_offset = 8 * res.node_count;
+    if (!dst) return RSD_OK;
+    if (capacity < *bytes) {
+        set_error("rsd_bvh_build_lbvh: capacity below the BVH size");
+        return RSD_ERR_INVALID_ARG;
+    }
+    std::memcpy(dst, words.data(), *bytes);
     return RSD_OK;
 }
 

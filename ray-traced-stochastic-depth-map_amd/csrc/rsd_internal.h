@@ -76,6 +76,24 @@ struct DynamicData {
     // rsd_scene_motion_begin_frame; an allocation of its own (rsd_scene.motion_bytes), null when not tracked
     float* prev_positions = nullptr;
 };
+// The layout of rsd_scene.d_dyn for nt triangles, nv vertices and nn wide nodes: byte offsets of DynamicData's
+// arrays, each 256-byte aligned.  The per-node tables follow the per-scene ones, so a rebuilt tree
+// (rsd_scene_rebuild_bvh) keeps the order with another node count.
+struct DynLayout {
+    size_t indices, positions, parent, inner, arrive, tight, total;
+};
+inline DynLayout dyn_layout(uint32_t nt, uint32_t nv, uint32_t nn) {
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    DynLayout l;
+    l.indices = 0;
+    l.positions = al(12 * (size_t)nt);
+    l.parent = l.positions + al(12 * (size_t)nv);
+    l.inner = l.parent + al(4 * (size_t)nn);
+    l.arrive = l.inner + al(4 * (size_t)nn);
+    l.tight = l.arrive + al(4 * (size_t)nn);
+    l.total = l.tight + al(24 * (size_t)nn);
+    return l;
+}
 
 // The rig of a dynamic scene (rsd_scene_attach_rig, csrc/skinning.hip): pointers into rsd_scene.d_rig, one
 // allocation.  Every id in it was checked on the host at attach.
@@ -142,6 +160,9 @@ struct rsd_scene {
     void* d_morph = nullptr;
     rsd::MorphData morph;
     uint64_t morph_bytes = 0;
+    // rsd_scene_rebuild_bvh calls that succeeded, and the last one's time on the device
+    uint64_t rebuilds = 0;
+    double rebuild_ms = 0.0;
 };
 
 namespace rsd {
@@ -166,6 +187,9 @@ inline dim3 image_grid(uint32_t w, uint32_t h, uint32_t layers = 1) {
 rsd_status refit_scatter_enqueue(rsd_scene* s, const uint32_t* d_ids, const float* d_positions, uint32_t count,
                                  hipStream_t st);
 rsd_status refit_enqueue(rsd_scene* s, hipStream_t st);
+// lbvh.hip: rsd_scene_rebuild_bvh on a dynamic scene -- waits for the device, builds the LBVH of the current
+// positions (csrc/lbvh.h) into new allocations, swaps it into `s`, refits its boxes and frees the old tree
+rsd_status lbvh_rebuild(rsd_scene* s);
 // prev_positions <- positions of a scene that tracks motion, one launch on `st`
 rsd_status motion_snapshot_enqueue(rsd_scene* s, hipStream_t st);
 // skinning.hip: pose the rig's vertices into the scene's position copy from `d_matrices` (float[matrix_count][12]);

@@ -62,6 +62,11 @@ class SceneDynamicInfo(C.Structure):  # rsd_scene_dynamic_info
                 ("dynamic_bytes", C.c_uint64)]
 
 
+class SceneRebuildInfo(C.Structure):  # rsd_scene_rebuild_info
+    _fields_ = [("rebuilds", C.c_uint64), ("node_count", C.c_uint32), ("wide_depth", C.c_uint32),
+                ("device_ms", C.c_double)]
+
+
 class RigDesc(C.Structure):  # rsd_rig_desc
     _fields_ = [("count", C.c_uint32), ("matrix_count", C.c_uint32), ("vertex_ids", C.c_void_p),
                 ("matrix_ids", C.c_void_p), ("weights", C.c_void_p), ("rest_positions", C.c_void_p)]
@@ -305,7 +310,8 @@ EXPORTS = ["rsd_abi_version", "rsd_svao_tile_count", "rsd_sd_tile_state_count", 
            "rsd_scene_update_subset", "rsd_scene_rebuild_entry_grid", "rsd_scene_dynamic_info_get", "rsd_bvh_refit",
            "rsd_scene_attach_rig", "rsd_scene_update_pose", "rsd_scene_rig_info_get", "rsd_scene_track_motion",
            "rsd_scene_motion_begin_frame", "rsd_scene_motion_info_get", "rsd_gbuffer_motion",
-           "rsd_scene_attach_morph", "rsd_scene_update_pose_morph", "rsd_scene_morph_info_get"]
+           "rsd_scene_attach_morph", "rsd_scene_update_pose_morph", "rsd_scene_morph_info_get",
+           "rsd_scene_rebuild_bvh", "rsd_scene_rebuild_info_get", "rsd_bvh_build_lbvh"]
 
 SD_CONSUME_INTERVALS = 1
 SD_THROUGHPUT = 2  # frames in flight: the work-efficient traversal (rsd.h RSD_SD_THROUGHPUT)
@@ -392,6 +398,12 @@ def lib(allow_missing=()):
         L.rsd_scene_motion_begin_frame.argtypes = [vp, vp]
         L.rsd_scene_motion_info_get.restype = st
         L.rsd_scene_motion_info_get.argtypes = [vp, C.POINTER(SceneMotionInfo)]
+        L.rsd_scene_rebuild_bvh.restype = st
+        L.rsd_scene_rebuild_bvh.argtypes = [vp]
+        L.rsd_scene_rebuild_info_get.restype = st
+        L.rsd_scene_rebuild_info_get.argtypes = [vp, C.POINTER(SceneRebuildInfo)]
+        L.rsd_bvh_build_lbvh.restype = st
+        L.rsd_bvh_build_lbvh.argtypes = [C.POINTER(SceneDesc), vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(u32)]
         L.rsd_bvh_refit.restype = st
         L.rsd_bvh_refit.argtypes = [vp, C.c_uint64, u32, vp, u32, vp, u32, vp]
         L.rsd_ray_cone_spread.restype = f32

@@ -200,6 +200,19 @@ def host_bvh(scene: Scene):
     return buf, off.value
 
 
+def host_bvh_lbvh(scene: Scene):
+    """The LBVH of `scene` built on the host without a GPU (rsd_bvh_build_lbvh): the bytes GpuScene.rebuild_bvh()
+    leaves on the device for these positions, as (float32 array, triangle-record offset in float4 units)."""
+    desc = abi.SceneDesc(scene.positions.ctypes.data, scene.positions.shape[0], scene.indices.ctypes.data,
+                         scene.indices.shape[0], scene.flags.ctypes.data)
+    n, off = C.c_uint64(), C.c_uint32()
+    abi.check(abi.lib().rsd_bvh_build_lbvh(C.byref(desc), None, 0, C.byref(n), C.byref(off)), "rsd_bvh_build_lbvh")
+    buf = np.zeros(n.value // 4, np.float32)
+    abi.check(abi.lib().rsd_bvh_build_lbvh(C.byref(desc), buf.ctypes.data, n.value, C.byref(n), C.byref(off)),
+              "rsd_bvh_build_lbvh")
+    return buf, off.value
+
+
 def host_bvh_refit(bvh, tri_offset: int, indices, positions):
     """rsd_bvh_refit: the BVH bytes `bvh` (float32 array of host_bvh() or GpuScene.export_bvh()) refitted to
     `positions` on the host, as a new float32 array -- what an update of a dynamic scene leaves on the device."""
@@ -398,6 +411,18 @@ class GpuScene:
         abi.check(abi.lib().rsd_scene_rebuild_entry_grid(self.h), "rsd_scene_rebuild_entry_grid")
         abi.check(abi.lib().rsd_scene_info_get(self.h, C.byref(self.info)), "rsd_scene_info_get")
 
+    def rebuild_bvh(self):
+        """Build a new tree over the scene's current positions on the GPU, in place (rsd_scene_rebuild_bvh;
+        synchronous): the bytes are host_bvh_lbvh's.  Rig, morph table, alpha data and motion tracking stay; the
+        entry grid is stale until rebuild_entry_grid()."""
+        abi.check(abi.lib().rsd_scene_rebuild_bvh(self.h), "rsd_scene_rebuild_bvh")
+        abi.check(abi.lib().rsd_scene_info_get(self.h, C.byref(self.info)), "rsd_scene_info_get")
+
+    def rebuild_info(self) -> abi.SceneRebuildInfo:
+        d = abi.SceneRebuildInfo()
+        abi.check(abi.lib().rsd_scene_rebuild_info_get(self.h, C.byref(d)), "rsd_scene_rebuild_info_get")
+        return d
+
     def dynamic_info(self) -> abi.SceneDynamicInfo:
         d = abi.SceneDynamicInfo()
         abi.check(abi.lib().rsd_scene_dynamic_info_get(self.h, C.byref(d)), "rsd_scene_dynamic_info_get")
@@ -538,6 +563,10 @@ class Renderer:
         self.gscene.update_positions(positions, stream=self.stream)
         host = positions.detach().cpu().numpy() if hasattr(positions, "data_ptr") else positions
         self.scene = dataclasses.replace(self.scene, positions=np.array(host, np.float32).reshape(-1, 3))
+
+    def rebuild_bvh(self):
+        """A new tree over the scene's current positions (GpuScene.rebuild_bvh; synchronous)."""
+        self.gscene.rebuild_bvh()
 
     def animate(self, t):
         """The scene at animation time t (GpuScene.animate on this renderer's stream).  self.scene.positions keeps

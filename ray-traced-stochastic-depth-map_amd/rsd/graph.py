@@ -122,6 +122,11 @@ class RenderGraph:
                   "rsd_graph_update_scene_positions")
         self._keep = [pos]
 
+    def rebuild_bvh(self):
+        """A new tree over the current positions of the graph's scene (rsd_scene_rebuild_bvh on the scene itself;
+        synchronous): passes read the scene's device tree every execute, so the next execute walks the new one."""
+        abi.check(abi.lib().rsd_scene_rebuild_bvh(self._scene_h), "rsd_scene_rebuild_bvh")
+
     def update_pose(self, matrices, stream=None):
         """Pose the rig of the graph's scene on `stream` (rsd_graph_update_scene_pose): matrices is float32
         [matrix_count, 12], a numpy array (kept alive here until the next update) or a torch tensor on the device."""
