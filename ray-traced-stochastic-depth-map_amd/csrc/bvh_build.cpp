@@ -46,6 +46,15 @@ struct TNode {             // temporary binary-tree node
 };
 
 constexpr int kBins = 32;
+// The bin of a centroid `c` in a centroid box that starts at `lo`: (c - lo) * scale truncated and clamped to
+// [0, kBins).  A centroid extent of denormal size makes scale infinite and one that overflows float32 makes it 0:
+// the product is then infinite or NaN, whose conversion to int is undefined (it came out negative and indexed in
+// front of the bins).  Such values are clamped before the conversion, a NaN to bin 0; every other scene bins as before.
+inline int sah_bin(float c, float lo, float scale) {
+    const float f = (c - lo) * scale;
+    if (!(f >= 0.0f)) return 0;
+    return f < (float)kBins ? (int)f : kBins - 1;
+}
 constexpr double kTraversalCostDefault = 1.0;  // relative to one triangle test
 // RSD_BVH_TCOST overrides the SAH traversal cost (build-quality experiments; results do not depend
 // on the tree for canonical traces)
@@ -110,7 +119,7 @@ struct Builder {
                 const float scale = (float)kBins / ext;
                 for (uint32_t i = first; i < first + count; ++i) {
                     uint32_t t = order[i];
-                    int b = std::min(kBins - 1, (int)((cent[3 * t + axis] - cb.lo[axis]) * scale));
+                    int b = sah_bin(cent[3 * t + axis], cb.lo[axis], scale);
                     bb[b].grow(tb[t]);
                     bc[b]++;
                 }
@@ -142,7 +151,7 @@ struct Builder {
             const float ext = cb.hi[bestAxis] - cb.lo[bestAxis];
             const float scale = (float)kBins / ext;
             auto mid = std::partition(order.begin() + first, order.begin() + first + count, [&](uint32_t t) {
-                int b = std::min(kBins - 1, (int)((cent[3 * t + bestAxis] - cb.lo[bestAxis]) * scale));
+                int b = sah_bin(cent[3 * t + bestAxis], cb.lo[bestAxis], scale);
                 return b <= bestBin;
             });
             nleft = (uint32_t)(mid - (order.begin() + first));
@@ -272,7 +281,7 @@ struct SplitBuilder {
                 uint32_t bc[kBins] = {0};
                 const float scale = (float)kBins / ext;
                 for (const Ref& r : refs) {
-                    const int b = std::min(kBins - 1, (int)((centroid(r, axis) - cb.lo[axis]) * scale));
+                    const int b = sah_bin(centroid(r, axis), cb.lo[axis], scale);
                     bb[b].grow(r.box);
                     bc[b]++;
                 }
@@ -410,7 +419,7 @@ struct SplitBuilder {
             const float ext = cb.hi[oAxis] - cb.lo[oAxis];
             const float scale = (float)kBins / ext;
             for (const Ref& r : refs) {
-                const int b = std::min(kBins - 1, (int)((centroid(r, oAxis) - cb.lo[oAxis]) * scale));
+                const int b = sah_bin(centroid(r, oAxis), cb.lo[oAxis], scale);
                 (b <= oBin ? left : right).push_back(r);
             }
             done = !left.empty() && !right.empty();

@@ -281,3 +281,128 @@ def test_bad_tables_are_refused_and_the_scene_still_poses(gpu, grid):
         _assert_canaries(have, grid)
     finally:
         gs.release()
+
+
+# ------------------------------------------------------------------ the float mode of pose_kernel<*, true>
+# The inputs above are of order 1.  Here the products w * delta are denormal, overflow, or carry a NaN; bytes only.
+
+TINY = np.finfo(F).tiny
+
+
+def _signed(rng, lo, hi, shape):
+    return rng.choice([-1.0, 1.0], shape) * rng.uniform(lo, hi, shape)
+
+
+def _edge_rig(grid, rest):
+    from rsd.animation import Rig
+    base = _rig(grid, 257, seed=5)
+    return Rig(base.vertex_ids, base.matrix_ids, base.weights, NM, rest=np.ascontiguousarray(rest, F))
+
+
+def _pose_morph_and_read(gpu, grid, rig, morph, M, w):
+    from rsd.frame import GpuScene
+    gs = GpuScene(gpu, grid, dynamic=True)
+    try:
+        gs.attach_rig(rig)
+        gs.attach_morph(morph)
+        gs.update_pose_morph(M, w)
+        return morph_checker.export_positions(gs, grid.indices), gs.export_bvh()[0]
+    finally:
+        gs.release()
+
+
+def _refit_bytes(grid, positions):
+    from rsd.frame import host_bvh, host_bvh_refit
+    built, off = host_bvh(grid)
+    return host_bvh_refit(built, off, grid.indices, positions)
+
+
+def test_morph_keeps_denormal_products(gpu, grid, table_variant):
+    """Weights and deltas of about 1e-20 on rest coordinates of about 1e-39: every product w * delta is denormal and
+    so is the sum it is added to.  Matrices 0 and 1 have no translation, so their vertices stay denormal through the
+    pose; 2 and 3 give normal words.  Counted on the checker's output first; a build that flushed float32 denormals
+    would add zeros and pose zeros."""
+    from rsd.animation import MorphTable
+    rng = np.random.default_rng(50)
+    rig = _edge_rig(grid, _signed(rng, 1e-39, 9e-39, (257, 3)))
+    base, _ = _table(257, 7, seed=3)
+    deltas = _signed(rng, 0.5e-20, 2e-20, base.deltas.shape).astype(F)
+    morph = MorphTable(base.offsets, base.weight_ids, deltas, 7)
+    w = _signed(rng, 0.5e-20, 2e-20, 7).astype(F)
+    M = skinning_checker.random_matrices(rng, NM, translation=0.5)
+    M[:2, [3, 7, 11]] = 0
+    want = morph_checker.posed(grid.positions, rig, M, morph.offsets, morph.weight_ids, morph.deltas, w)
+    plain = skinning_checker.posed(grid.positions, rig, M)
+    assert (_u32(want) != _u32(plain)).sum() >= 32, "the denormal products show in the result"
+    mag = np.abs(want[rig.vertex_ids].astype(np.float64))
+    denormal, normal = (mag > 0) & (mag < TINY), (mag >= TINY) & np.isfinite(mag)
+    assert denormal.sum() >= 32 and normal.sum() >= 32, (denormal.sum(), normal.sum())
+    have, bvh = _pose_morph_and_read(gpu, grid, rig, morph, M, w)
+    bad = np.flatnonzero((_u32(have) != _u32(want)).any(axis=1))
+    assert bad.size == 0, (bad.size, bad[:8], have[bad[:2]], want[bad[:2]])
+    _assert_canaries(have, grid)
+    assert np.array_equal(_u32(bvh), _u32(_refit_bytes(grid, want)))
+
+
+def test_morph_overflows_to_both_infinities(gpu, grid, table_variant):
+    """Weight 2 is 3e38 and its deltas are (+-2, 0.01, 0.01), one sign per vertex: x overflows to that infinity, y and
+    z stay finite, no inf - inf arises, and no blended matrix has a zero in column 0.  Both infinities and no NaN in
+    the expected words; the comparison is bitwise throughout."""
+    from rsd.animation import MorphTable
+    rng = np.random.default_rng(51)
+    rig = _edge_rig(grid, grid.positions[PAD:PAD + 257])
+    base, w = _table(257, 7, seed=4)
+    owner = np.repeat(np.arange(257), np.diff(base.offsets.astype(np.int64)))
+    deltas = base.deltas.copy()
+    big = base.weight_ids == 2
+    assert big.sum() >= 32
+    deltas[big] = np.stack([np.where(owner[big] % 2 == 0, 2.0, -2.0), np.full(big.sum(), 0.01),
+                            np.full(big.sum(), 0.01)], 1).astype(F)
+    morph = MorphTable(base.offsets, base.weight_ids, deltas, 7)
+    w = w.copy()
+    w[2] = F(3e38)
+    M = skinning_checker.random_matrices(rng, NM, translation=0.5)
+    with np.errstate(over="ignore"):
+        want = morph_checker.posed(grid.positions, rig, M, morph.offsets, morph.weight_ids, morph.deltas, w)
+    out = want[rig.vertex_ids]
+    assert np.isposinf(out).any() and np.isneginf(out).any() and not np.isnan(out).any() and np.isfinite(out).sum() >= 32
+    have, bvh = _pose_morph_and_read(gpu, grid, rig, morph, M, w)
+    bad = np.flatnonzero((_u32(have) != _u32(want)).any(axis=1))
+    assert bad.size == 0, (bad.size, bad[:8], have[bad[:2]], want[bad[:2]])
+    _assert_canaries(have, grid)
+    assert np.array_equal(_u32(bvh), _u32(_refit_bytes(grid, want)))
+
+
+def test_morph_propagates_a_nan_weight_and_an_infinite_rest(gpu, grid, table_variant):
+    """Weight 6 is NaN and only the first entry of rig vertex 5 names it; rig vertex 9 has an infinite rest
+    coordinate.  Bit for bit the checker's except the six words of those two vertices where the checker holds a NaN:
+    there the kernel must hold a NaN too, of whatever payload (the host generates the negative default NaN for
+    inf - inf and 0 * inf, the GPU the positive one).  The tree is rsd_bvh_refit's at the checker's positions with
+    those NaN words in the device's payload."""
+    from rsd.animation import MorphTable
+    rng = np.random.default_rng(52)
+    rest = grid.positions[PAD:PAD + 257].copy()
+    rest[9, 1] = np.inf
+    rig = _edge_rig(grid, rest)
+    base, w = _table(257, 7, seed=6)
+    ids = base.weight_ids.copy()
+    ids[ids == 6] = 5
+    e = int(base.offsets[5])
+    assert base.offsets[6] - base.offsets[5] == 9
+    ids[e] = 6
+    morph = MorphTable(base.offsets, ids, base.deltas, 7)
+    w = w.copy()
+    w[6] = F(np.nan)
+    M = skinning_checker.random_matrices(rng, NM, translation=0.5)
+    with np.errstate(invalid="ignore"):
+        want = morph_checker.posed(grid.positions, rig, M, morph.offsets, morph.weight_ids, morph.deltas, w)
+    special = rig.vertex_ids[[5, 9]]
+    nan = np.isnan(want)
+    assert nan[special[0]].all() and not np.isfinite(want[special[1]]).any() and nan.sum() == nan[special].sum()
+    have, bvh = _pose_morph_and_read(gpu, grid, rig, morph, M, w)
+    assert np.array_equal(np.isnan(have), nan), "NaN exactly where the checker has one"
+    assert ((_u32(have) == _u32(want)) | nan).all(), "every other word bit for bit"
+    _assert_canaries(have, grid)
+    at = want.copy()
+    at[nan] = have[nan]
+    assert np.array_equal(_u32(bvh), _u32(_refit_bytes(grid, at)))

@@ -3,12 +3,15 @@
 All comparisons are bitwise.  The pose arithmetic is stated independently in tests/skinning_checker.py; what a pose
 leaves on the device is rsd_bvh_refit of the upload's tree at the checker's positions (the refit itself is pinned by
 tests/test_bvh_refit.py), and what is rendered from it equals a fresh static upload of those positions and the CPU
-oracle.  Frames are 75 x 45, exact numerics.  Every id handed to the device is valid: the refusals are host checks."""
+oracle.  Frames are 75 x 45, exact numerics.  Every id handed to the device is valid: the refusals are host checks.  The last three tests
+leave the inputs of order 1: denormal results, overflow, a NaN weight and an infinite rest coordinate."""
 import dataclasses
+import os
 
 import numpy as np
 import pytest
 
+import morph_checker
 import skinning_checker
 from helpers import oracle_frame, to_oracle
 
@@ -335,3 +338,117 @@ def test_gpu_scene_attaches_the_scenes_own_rig_and_animates(gpu):
         assert p.tobytes() == scene.positions.tobytes() and np.array_equal(_u32(have), _u32(built))
     finally:
         gs.release()
+
+
+# ------------------------------------------------------------------ the float mode of the pose kernel
+# csrc/skinning.hip is an exact kernel: every product and sum rounded on its own, denormals kept, non-finite values
+# propagated.  The inputs above are all of order 1; these are not.  Bytes only: no frame is rendered.
+
+TINY = np.finfo(np.float32).tiny
+
+
+@pytest.fixture(params=["global", "lds"])
+def table_variant(request):
+    prev = os.environ.get("RSD_POSE_TABLE")
+    os.environ["RSD_POSE_TABLE"] = request.param
+    yield request.param
+    if prev is None:
+        del os.environ["RSD_POSE_TABLE"]
+    else:
+        os.environ["RSD_POSE_TABLE"] = prev
+
+
+def _edge_rig(scene, rest):
+    base = _rig(scene.positions.shape[0], BLOCK + 1, "scattered", seed=31)
+    assert np.isin(base.vertex_ids, scene.indices).all(), "every rig vertex reads back from a triangle record"
+    return type(base)(base.vertex_ids, base.matrix_ids, base.weights, NM, rest=np.ascontiguousarray(rest, np.float32))
+
+
+def _signed(rng, lo, hi, shape):
+    return rng.choice([-1.0, 1.0], shape) * rng.uniform(lo, hi, shape)
+
+
+def _pose_and_read(gpu, scene, rig, M):
+    from rsd.frame import GpuScene
+    gs = GpuScene(gpu, scene, dynamic=True)
+    try:
+        gs.attach_rig(rig)
+        gs.update_pose(M)
+        return morph_checker.export_positions(gs, scene.indices), gs.export_bvh()[0]
+    finally:
+        gs.release()
+
+
+def test_pose_keeps_denormal_results(gpu, table_variant):
+    """Matrix entries of about 1e-25 and rest coordinates of about 1e-15: the blended products lie near 1e-40.
+    Matrices 0 .. 2 carry denormal translations, 3 and 4 normal ones, so the expected words are of both kinds -- counted
+    on the checker's output before the GPU is looked at (a numpy that flushed denormals fails here, and so it should).
+    A build of this file that flushed float32 denormals would store zeros where the checker has 1e-40."""
+    from rsd.frame import host_bvh, host_bvh_refit
+    scene = _shape_scene("arcade_3000")
+    rng = np.random.default_rng(40)
+    rig = _edge_rig(scene, _signed(rng, 0.5e-15, 2e-15, (BLOCK + 1, 3)))
+    M = (skinning_checker.random_matrices(rng, NM).astype(np.float64) * 1e-25).astype(np.float32)
+    M[:3, [3, 7, 11]] = _signed(rng, 1e-42, 9e-41, (3, 3)).astype(np.float32)
+    want = skinning_checker.posed(scene.positions, rig, M)
+    mag = np.abs(want[rig.vertex_ids].astype(np.float64))
+    denormal, normal = (mag > 0) & (mag < TINY), (mag >= TINY) & np.isfinite(mag)
+    assert denormal.sum() >= 32 and normal.sum() >= 32, (denormal.sum(), normal.sum())
+    have, bvh = _pose_and_read(gpu, scene, rig, M)
+    ref = np.unique(scene.indices)
+    bad = np.flatnonzero((_u32(have[ref]) != _u32(want[ref])).any(axis=1))
+    assert bad.size == 0, (bad.size, ref[bad[:4]], have[ref[bad[:4]]], want[ref[bad[:4]]])
+    built, off = host_bvh(scene)
+    assert np.array_equal(_u32(bvh), _u32(host_bvh_refit(built, off, scene.indices, want)))
+
+
+def test_pose_overflows_to_both_infinities(gpu, table_variant):
+    """One matrix carries 3e38 on its diagonal: where its weights sum past 1 the blend overflows, and where the rest
+    coordinate is above 1.14 the product does.  One huge entry per row and no zero rest coordinate: no inf - inf and no
+    0 * inf, so the expected words hold both infinities and no NaN, and the comparison is bitwise throughout."""
+    from rsd.frame import host_bvh, host_bvh_refit
+    scene = _shape_scene("arcade_3000")
+    rng = np.random.default_rng(41)
+    rig = _edge_rig(scene, _signed(rng, 1.3, 2.0, (BLOCK + 1, 3)))
+    M = skinning_checker.random_matrices(rng, NM)
+    M[NM - 1] = np.float32([3e38, 0.5, 0.25, 0.1, 0.3, -3e38, 0.2, 0.1, 0.1, 0.2, 3e38, 0.0])
+    with np.errstate(over="ignore"):
+        want = skinning_checker.posed(scene.positions, rig, M)
+    out = want[rig.vertex_ids]
+    assert np.isposinf(out).any() and np.isneginf(out).any() and not np.isnan(out).any() and np.isfinite(out).sum() >= 32
+    have, bvh = _pose_and_read(gpu, scene, rig, M)
+    ref = np.unique(scene.indices)
+    bad = np.flatnonzero((_u32(have[ref]) != _u32(want[ref])).any(axis=1))
+    assert bad.size == 0, (bad.size, ref[bad[:4]], have[ref[bad[:4]]], want[ref[bad[:4]]])
+    built, off = host_bvh(scene)
+    assert np.array_equal(_u32(bvh), _u32(host_bvh_refit(built, off, scene.indices, want)))
+
+
+def test_pose_propagates_a_nan_weight_and_an_infinite_rest(gpu, table_variant):
+    """Rig vertex 5 has a NaN weight, rig vertex 9 an infinite rest coordinate.  Everything is compared bit for bit
+    with the checker except the six words of those two vertices where the checker holds a NaN: there the kernel must
+    hold a NaN too, of whatever payload (numpy on the host generates the negative default NaN for inf - inf and
+    0 * inf, the GPU the positive one).  The tree is rsd_bvh_refit's at the checker's positions with those NaN words
+    in the device's payload."""
+    from rsd.frame import host_bvh, host_bvh_refit
+    scene = _shape_scene("arcade_3000")
+    rng = np.random.default_rng(42)
+    rest = _signed(rng, 0.5, 2.0, (BLOCK + 1, 3))
+    rest[9, 2] = np.inf
+    rig = _edge_rig(scene, rest)
+    rig.weights[5, 1] = np.nan
+    A, _, _ = _poses(13)
+    with np.errstate(invalid="ignore"):
+        want = skinning_checker.posed(scene.positions, rig, A)
+    special = rig.vertex_ids[[5, 9]]
+    nan = np.isnan(want)
+    assert nan[special[0]].all() and not np.isfinite(want[special[1]]).any() and nan.sum() == nan[special].sum()
+    have, bvh = _pose_and_read(gpu, scene, rig, A)
+    ref = np.unique(scene.indices)
+    assert np.array_equal(np.isnan(have[ref]), nan[ref]), "NaN exactly where the checker has one"
+    same = _u32(have) == _u32(want)
+    assert (same | nan)[ref].all(), "every other word bit for bit"
+    at = want.copy()
+    at[nan] = have[nan]
+    built, off = host_bvh(scene)
+    assert np.array_equal(_u32(bvh), _u32(host_bvh_refit(built, off, scene.indices, at)))
