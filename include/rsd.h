@@ -78,7 +78,8 @@ typedef struct {
  * material's constant alpha); the hit is alpha-tested away when opacity < alpha_threshold
  * (the threshold is stored as float16 like MaterialHeader, MaterialData.slang:99).
  * Textures are R8 (alpha only), row-major, mip 0; librsd builds the 2x2 box-filter mip chain.
- * Sampling: trilinear, wrap, 8 sub-texel / LOD-fraction bits (DESIGN.md "Alpha test"). */
+ * Sampling: trilinear, wrap, 8 sub-texel / LOD-fraction bits (DESIGN.md "Alpha test").
+ * A NaN opacity (constant alpha) or a NaN alpha_threshold keeps the hit: `opacity < alpha_threshold` is false. */
 #define RSD_NO_TEXTURE 0xffffffffu
 typedef struct {
     uint32_t width, height;
@@ -90,7 +91,13 @@ typedef struct {
     uint32_t texture;      /* index into rsd_alpha_desc.textures or RSD_NO_TEXTURE */
 } rsd_material;
 typedef struct {
-    const float* texcoords;            /* float2[vertex_count] (indexed like the positions) */
+    /* float2[vertex_count] (indexed like the positions).  Contract: every component of a vertex that a triangle flagged
+     * RSD_TRI_ALPHA_MASK with a textured material names is finite and within [-32768, 32768] (textures are at most
+     * 32768 wide, so |u W| + 2 <= 2^30 + 2 fits the sampler's int with a factor of two left for the interpolation's
+     * rounding); rsd_scene_upload_alpha / rsd_scene_upload_dynamic refuse the upload otherwise (RSD_ERR_INVALID_ARG,
+     * the message names the vertex), before any device work.  The texcoords of other vertices are never read by a
+     * kernel and are not checked. */
+    const float* texcoords;
     const uint32_t* triangle_material; /* uint32[triangle_count] */
     const rsd_material* materials;
     uint32_t material_count;

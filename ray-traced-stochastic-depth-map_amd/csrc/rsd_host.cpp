@@ -259,7 +259,8 @@ rsd_status scene_upload(rsd_device* dev, const rsd_scene_desc* desc, rsd_scene**
 
 namespace {
 // MaterialHeader stores the alpha threshold as float16 (MaterialData.slang:99): round to
-// nearest even at half precision, then widen.
+// nearest even at half precision, then widen.  A NaN threshold stays a NaN: `alpha < threshold` is then false and the
+// hit is kept (rsd.h rsd_material).
 float round_half(float f) {
     if (f != f) return f;
     const float a = std::fabs(f);
@@ -325,6 +326,26 @@ rsd_status scene_upload_alpha(rsd_device* dev, const rsd_scene_desc* desc, const
         if (alpha->triangle_material[i] >= alpha->material_count) {
             set_error("rsd_scene_upload_alpha: triangle_material out of range of material_count");
             return RSD_ERR_INVALID_ARG;
+        }
+    // the texcoord contract (rsd.h rsd_alpha_desc.texcoords): tex_split (tex_sample.h) converts floor(u W - 0.5) to an
+    // int, W <= 32768, so a sampled coordinate is finite and within +-32768 -- |u W| + 2 <= 2^30 + 2, a factor of two
+    // below INT_MAX for the interpolation's rounding.  Only the vertices of textured alpha-masked triangles are sampled.
+    // (An index past vertex_count is scene_upload's to refuse.)
+    if (desc->triangle_flags && desc->indices && alpha->texcoords)
+        for (uint32_t t = 0; t < desc->triangle_count; ++t) {
+            if (!(desc->triangle_flags[t] & RSD_TRI_ALPHA_MASK) ||
+                alpha->materials[alpha->triangle_material[t]].texture == RSD_NO_TEXTURE)
+                continue;
+            for (int j = 0; j < 3; ++j) {
+                const uint32_t v = desc->indices[3 * (size_t)t + j];
+                if (v >= desc->vertex_count) continue;
+                const float tu = alpha->texcoords[2 * (size_t)v], tv = alpha->texcoords[2 * (size_t)v + 1];
+                if (!(std::fabs(tu) <= 32768.0f) || !(std::fabs(tv) <= 32768.0f)) {  // false for a NaN
+                    set_error("rsd_scene_upload_alpha: vertex " + std::to_string(v) + " (triangle " + std::to_string(t) +
+                              ") has a texcoord that is not finite or outside [-32768, 32768]");
+                    return RSD_ERR_INVALID_ARG;
+                }
+            }
         }
     rsd_status st = scene_upload(dev, desc, out, dynamic);
     if (st != RSD_OK) return st;

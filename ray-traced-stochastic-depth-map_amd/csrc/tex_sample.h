@@ -42,7 +42,10 @@ RSD_HD TexAxis tex_split_axis(float x) {
 
 // The bilinear footprint of (u, v) on a W x H texture: its taps are (ix, iy), (ix + 1, iy), (ix, iy + 1),
 // (ix + 1, iy + 1) BEFORE addressing (they may lie outside the texture: tex_addr), weighted by wx, wy.
-// Precondition: u W and v H are finite and within int range.
+// Precondition: u W and v H are finite and within int range ((int)floorf of anything else is undefined on the host
+// and saturates on the device).  The alpha test's coordinates meet it by the upload's contract: rsd_scene_upload_alpha
+// refuses a sampled texcoord that is not finite or exceeds 32768 in magnitude (rsd.h rsd_alpha_desc.texcoords), and
+// W, H <= 32768.
 struct TexSplit {
     int ix, iy;
     float qx, qy, wx, wy;

@@ -12,6 +12,8 @@ import math
 import numpy as np
 import pytest
 
+import alpha_checker as AC
+
 F = np.float32
 
 
@@ -38,48 +40,17 @@ def test_threshold_is_float16(oracle):
     thr = [0.33, 0.1, 0.7777, 0.5, 1e-5, 0.999]
     mats = []
     for t in thr:
-        h = F(np.float16(t))
+        h = AC.half(t)
         mats += [(t, float(h), NO_TEXTURE), (t, float(np.nextafter(h, F(-1))), NO_TEXTURE)]
     sc, _ = _tri_scene(oracle, mats, [])
     for i, t in enumerate(thr):
-        assert sc.alpha_threshold(2 * i) == F(np.float16(t))
+        assert sc.alpha_threshold(2 * i) == AC.half(t) == F(np.float16(t))
         assert not sc.alpha_fails(2 * i, 0.2, 0.2)
         assert sc.alpha_fails(2 * i + 1, 0.2, 0.2)
 
 
-def _np_texel(tex, x, y):
-    h, w = tex.shape
-    return F(tex[y % h, x % w]) / F(255.0)
-
-
-def _np_bilinear(tex, u, v):
-    h, w = tex.shape
-    x, y = F(u) * F(w) - F(0.5), F(v) * F(h) - F(0.5)
-    x0, y0 = np.floor(x), np.floor(y)
-    qx, qy = np.floor((x - x0) * F(256.0) + F(0.5)), np.floor((y - y0) * F(256.0) + F(0.5))
-    ix, iy = int(x0), int(y0)
-    if qx >= 256:
-        qx, ix = F(0), ix + 1
-    if qy >= 256:
-        qy, iy = F(0), iy + 1
-    wx, wy = qx * F(1 / 256), qy * F(1 / 256)
-    r0 = _np_texel(tex, ix, iy) * (F(1) - wx) + _np_texel(tex, ix + 1, iy) * wx
-    r1 = _np_texel(tex, ix, iy + 1) * (F(1) - wx) + _np_texel(tex, ix + 1, iy + 1) * wx
-    return r0 * (F(1) - wy) + r1 * wy
-
-
-def _np_mips(tex):
-    chain = [tex.astype(np.int64)]
-    while chain[-1].shape != (1, 1):
-        a = chain[-1]
-        h, w = a.shape
-        nh, nw = max(1, h // 2), max(1, w // 2)
-        ys, xs = np.arange(nh), np.arange(nw)
-        y0, y1 = np.minimum(2 * ys, h - 1), np.minimum(2 * ys + 1, h - 1)
-        x0, x1 = np.minimum(2 * xs, w - 1), np.minimum(2 * xs + 1, w - 1)
-        s = a[y0][:, x0] + a[y0][:, x1] + a[y1][:, x0] + a[y1][:, x1]
-        chain.append((s + 2) // 4)
-    return [c.astype(np.uint8) for c in chain]
+# the bilinear tap, the box mip chain, the float16 threshold and the LOD split: tests/alpha_checker.py
+_np_bilinear, _np_mips = AC.bilinear, AC.mips
 
 
 @pytest.mark.parametrize("shape", [(8, 8), (5, 7), (1, 9), (16, 3)])
@@ -128,11 +99,7 @@ def test_ray_cone_lod_trilinear(oracle):
         tu, tv = F(0) * w0 + F(1) * bu + F(0) * bv, F(0) * w0 + F(0) * bu + F(1) * bv
         lam = F(0) + F(math.log2(float(abs(spread * t + F(0)) / abs(F(-1.0)))))
         level = F(0.5) * F(math.log2(float(F(256)))) + lam
-        lod = min(max(level, F(0)), F(len(mips) - 1))
-        l0 = int(np.floor(lod))
-        qf = np.floor((lod - F(l0)) * F(256) + F(0.5))
-        if qf >= 256:
-            l0, qf = l0 + 1, F(0)
+        l0, qf = AC.lod_split(level, len(mips))
         s0 = _np_bilinear(mips[l0], tu, tv)
         want = s0 if qf == 0 or l0 + 1 >= len(mips) else \
             s0 * (F(1) - qf * F(1 / 256)) + _np_bilinear(mips[l0 + 1], tu, tv) * (qf * F(1 / 256))
